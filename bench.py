@@ -11,6 +11,11 @@ checked against the exact oracle (|R| for unique keys).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--inner 1e9] [--outer 1e9]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run measures the headline only.  --full adds the secondary
+measurements (general_path, scale_model and, at N > 1, shuffle_path), each a
+run of its own.  --dump-outputs DIR writes what the last timed join returned
+(its match counts) as DIR/matches.npy.
 """
 import argparse
 import gc
@@ -417,10 +422,17 @@ def main():
     ap.add_argument("--input", default="device", choices=["device", "pinned"],
                     help="where the relations live: HBM, or pinned host memory read in place over the host link")
     ap.add_argument("--general", default="on", choices=["on", "off", "only"],
-                    help="also time the general path: the same join on sparse random 63-bit keys "
-                         "(only: just that, for sweeps)")
+                    help="with --full, also time the general path: the same join on sparse random 63-bit keys "
+                         "(only: the headline itself runs on those keys, for sweeps)")
     ap.add_argument("--scale-model", default="on", choices=["on", "off"],
-                    help="N = 1 only: predicted N = 2/4/8 step times of the three N > 1 paths (scale_model)")
+                    help="with --full, N = 1 only: predicted N = 2/4/8 step times of the three N > 1 paths "
+                         "(scale_model)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (shuffle_path, general_path, scale_model); a plain "
+                         "run times the headline join only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed join returned as DIR/matches.npy "
+                         "(float64: global_matches, local_matches, output_pairs of rank 0)")
     ap.add_argument("--json-out", default="")
     ap.add_argument("--budget-s", type=float, default=float(os.environ.get("HPCJOIN_BENCH_BUDGET_S", "420")),
                     help="wall budget of the whole run: the secondary measurements (shuffle_path, general_path, "
@@ -465,6 +477,14 @@ def main():
     head = measure(C, info, ctx, comm, on_gpu, G_R, G_S, *specs(args.general == "only"), cfg, rel_loc, args.steps,
                    args.warmup)
     join, results = head.pop("join"), head.pop("results")
+    if args.dump_outputs and info.rank == 0:
+        # What a caller of HashJoin.run() receives from the last timed join:
+        # its match counts (exact in float64 up to 2^53).
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        last = results[-1]
+        np.save(os.path.join(args.dump_outputs, "matches.npy"),
+                np.array([last["global_matches"], last["local_matches"], last["output_pairs"]], dtype=np.float64))
     plan = join.plan
     engine = {"reruns": results[-1]["reruns"], "build_probe_items": results[-1]["build_probe_items"],
               "network_fallbacks": sum(r["network_fallbacks"] for r in results),
@@ -503,7 +523,7 @@ def main():
     skipped = {}
     shuffle = None
     comm_ok = True
-    if info.world > 1 and plan.bitmap_replicated and budget_left("shuffle_path"):
+    if args.full and info.world > 1 and plan.bitmap_replicated and budget_left("shuffle_path"):
         # The reference's own N > 1 algorithm on the headline workload: hash-
         # partition shuffle (claim scatter + chunked RCCL all-to-allv, the
         # MPI_Put analog) instead of the replicated bitmaps the planner prefers.
@@ -527,7 +547,8 @@ def main():
             print(f"bench.py: shuffle path failed on rank {info.rank}: {e}", file=sys.stderr, flush=True)
 
     general = None
-    if args.general == "on" and args.dist in ("unique", "uniform", "zipf") and comm_ok and budget_left("general_path"):
+    if (args.full and args.general == "on" and args.dist in ("unique", "uniform", "zipf") and comm_ok
+            and budget_left("general_path")):
         # The secondary measurement must not cost the headline line: a failure
         # here (the engine aborts the communicator on every rank) is reported
         # in general_path and the headline is still printed.
@@ -547,7 +568,7 @@ def main():
             print(f"bench.py: general path failed on rank {info.rank}: {e}", file=sys.stderr, flush=True)
 
     model = None
-    if (args.scale_model == "on" and info.world == 1 and on_gpu and args.dist == "unique" and comm_ok
+    if (args.full and args.scale_model == "on" and info.world == 1 and on_gpu and args.dist == "unique" and comm_ok
             and budget_left("scale_model")):
         try:
             model = scale_model(C, info, ctx, comm, on_gpu, G_R, G_S, specs, cfg, rel_loc, args.general != "off")
@@ -605,6 +626,7 @@ def main():
             "general_path": general,
             "scale_model": model,
             "engine": engine,
+            "full": args.full,
             "skipped": skipped or None,
             "wall_s": round(time.time() - T_START, 1),
             "comm_timeout_s": float(os.environ.get("HPCJOIN_COMM_TIMEOUT_S", "600")),

@@ -49,6 +49,28 @@ def test_bench_py_cpu_contract():
     assert "value_note" in j  # which plan `value` measures (N > 1: replicated bitmaps, not the shuffle)
 
 
+def test_bench_py_plain_run_is_headline_only_and_dumps(tmp_path):
+    """Without --full only the headline join is measured; --dump-outputs writes
+    the last timed join's match counts, identical from run to run."""
+    import numpy as np
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
+    dumps = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", str(tmp_path / name)],
+                           capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0, r.stdout + r.stderr
+        j = _last_json(r.stdout)
+        assert j["full"] is False and j["steps"] == 3 and j["ms_per_step"] > 0
+        assert j["general_path"] is None and j["scale_model"] is None and j["shuffle_path"] is None
+        assert len(j["engine"]["step_ms"]) == 3  # --steps is the number of timed joins
+        assert [p.name for p in (tmp_path / name).iterdir()] == ["matches.npy"]
+        dumps.append(np.load(tmp_path / name / "matches.npy"))
+        assert dumps[-1].dtype == np.float64
+        assert dumps[-1][0] == j["matches"] == j["expected_matches"]
+    assert np.array_equal(dumps[0], dumps[1])
+
+
 def test_bench_py_stalled_rank_exits_with_site(tmp_path):
     """bench.py --gpus 2 (its own spawner, gloo on the CPU) with rank 1 stalled
     at `network`: both ranks end within the watchdog timeout, the job exits
@@ -71,7 +93,7 @@ def test_bench_py_wall_budget_skips_secondary():
     instead of running past the driver's limit; the headline is printed."""
     env = dict(os.environ, HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1",
-                        "--budget-s", "0"], capture_output=True, text=True, timeout=300, env=env)
+                        "--full", "--budget-s", "0"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
     j = _last_json(r.stdout)
     assert j["correct"] is True and j["general_path"] is None
