@@ -173,7 +173,7 @@ def build_sanitized(kind: str = "address", jobs: int | None = None, verbose: boo
     def compile_kernel(src):
         # The kernels are not sanitized: the main build's object of the same
         # source, headers and flags is reused when it exists (a gfx950 compile
-        # of partition.hip takes minutes).
+        # of the scatter files takes a minute or more each).
         main = _obj(src, kflags, hdr)
         if main.exists():
             return main

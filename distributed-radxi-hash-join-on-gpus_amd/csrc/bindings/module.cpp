@@ -700,7 +700,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readwrite("split_histogram", &core::JoinConfig::splitHistogram)
       .def_readwrite("pipeline_outer", &core::JoinConfig::pipelineOuter)
       .def_readwrite("local_item_tiles", &core::JoinConfig::localItemTiles)
-      .def_readwrite("local_geometry", &core::JoinConfig::localGeometry)
       .def_readwrite("local_sample_stride", &core::JoinConfig::localSampleStride)
       .def_readwrite("round_lp", &core::JoinConfig::roundLp)
       .def_readwrite("output_capacity", &core::JoinConfig::outputCapacity)
@@ -720,10 +719,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readwrite("workspace_budget", &core::JoinConfig::workspaceBudget)
       .def_readwrite("link_gbps_per_peer", &core::JoinConfig::linkGBpsPerPeer)
       // KernelVariants, flattened (sweeps / A-B tests; core/Types.h)
-      .def_property("net_ipt", [](const core::JoinConfig &c) { return c.variants.netIpt; },
-                    [](core::JoinConfig &c, uint32_t v) { c.variants.netIpt = v; })
-      .def_property("net_threads", [](const core::JoinConfig &c) { return c.variants.netThreads; },
-                    [](core::JoinConfig &c, uint32_t v) { c.variants.netThreads = v; })
       .def_property("bm_threads", [](const core::JoinConfig &c) { return c.variants.bmThreads; },
                     [](core::JoinConfig &c, uint32_t v) { c.variants.bmThreads = v; })
       .def_property("bm_flat", [](const core::JoinConfig &c) { return c.variants.bmFlat; },

@@ -38,7 +38,6 @@ JoinPlan makePlan(const JoinConfig &cfg, uint32_t numberOfNodes, uint64_t global
   p.materialize = cfg.materialize;
   p.directCount = cfg.directCount;
   p.localItemTiles = std::max<uint32_t>(1, std::min<uint32_t>(cfg.localItemTiles, 1024));
-  p.localGeometry = cfg.localGeometry;
   p.variants = cfg.variants;
   p.assignment = cfg.assignment;
   p.skewSplit = cfg.skewSplit && cfg.assignment == AssignmentPolicy::LPT && numberOfNodes > 1;

@@ -135,7 +135,6 @@ struct JoinConfig {
   // workspace to fit what HBM has free (capped by workspaceBudget).
   uint32_t passes = 0;
   uint32_t localItemTiles = 64; // local pass work item: up to this many 4096-tuple tiles of one segment
-  uint32_t localGeometry = 0;   // local scatter workgroup geometry (0 = 1024 x 8; 1-4: sweep alternatives)
   KernelVariants variants;      // kernel-shape variants (sweeps; core/Types.h)
   // Device engines: grow the workspace arena to the plan's size estimate at
   // HashJoin construction (and touch the new pages once), so that the first
@@ -206,7 +205,6 @@ struct JoinPlan {
   bool skewSplit = false;     // hot network partitions may be split across ranks
   bool directCount = true;    // build/probe may use direct-addressed count tables
   uint32_t localItemTiles = 64;
-  uint32_t localGeometry = 0;
   KernelVariants variants;
   uint32_t wireBits[2] = {0, 0};
   uint32_t wireRidBits[2] = {0, 0};

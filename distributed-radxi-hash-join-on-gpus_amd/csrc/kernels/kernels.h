@@ -2,11 +2,16 @@
 //
 // Kernel map vs the reference GPU library:
 //   datagen.hip      device relation generators (replace Relation.cpp:63-141)
-//   partition.hip    LDS radix histogram + LDS write-combining scatter, both
-//                    radix passes (network pass = NetworkPartitioning.cpp:74-222,
-//                    local pass = LocalPartitioning.cpp:138-250; supersede the
-//                    dormant histogram_build_L1/L2 + reorder_L1/L2 families of
-//                    kernels.cu / kernels_optimized.cu / kernels_tile.cu)
+//   scatter_core.h   device templates of the LDS write-combining scatter (policies,
+//                    scatterTile / scatterRange), shared by the three files below
+//   net_partition.hip    pass 1: LDS radix histograms, sampled totals and layout,
+//                    claim-mode scatter (NetworkPartitioning.cpp:74-222)
+//   local_partition.hip  pass 2: item histograms, cursors, sampled layout,
+//                    persistent claim scatter (LocalPartitioning.cpp:138-250);
+//                    the two supersede the dormant histogram_build_L1/L2 +
+//                    reorder_L1/L2 families of kernels.cu / kernels_optimized.cu /
+//                    kernels_tile.cu
+//   scatter_ablation.hip mode x geometry matrix of the scatter (micro-benchmarks)
 //   build_probe.hip  LDS hash build/probe over (partition, R-chunk, S-chunk)
 //                    work items (BuildProbe.cpp:47-121, eth.cu:25-109, and the
 //                    probe / probe_skew / probe_count / probe_match_rate family)
@@ -33,8 +38,6 @@ constexpr uint32_t MAX_PART_BITS = 11;   // LDS cursor/count arrays sized for 20
 struct PartitionGeometry {
   uint32_t blocks = 0;         // workgroups of the pass (each owns a contiguous tile range)
   uint32_t tilesPerBlock = 0;  // tiles per workgroup
-  uint32_t ipt = 0;            // claim-scatter tile variant (KernelVariants::netIpt; 0 = auto)
-  uint32_t nth = 0;            // claim-scatter workgroup width (KernelVariants::netThreads; 0 = 1024)
   uint64_t tuplesPerBlock() const { return uint64_t(tilesPerBlock) * PART_TILE; }
 };
 // Cap the grid at ~8 workgroups per CU (2048) and give each workgroup a
@@ -325,8 +328,7 @@ constexpr uint32_t SPLIT_BYTES = 6;
 // the u16 column of fragment >> bits alone (out; split.hi unused).
 void localScatter(const void *in, bool wide, const LocalItem *items, uint32_t nItems, uint32_t shift,
                   uint32_t bits, void *gcur, bool narrow, void *out, hipStream_t s, const void *gend = nullptr,
-                  SplitLayout split = SplitLayout(), uint32_t geometry = 0, bool frag = false,
-                  RoundMap rm = RoundMap());
+                  SplitLayout split = SplitLayout(), bool frag = false, RoundMap rm = RoundMap());
 // Sampled local pass (no exact local histogram): itemHist from
 // localHistogram(sampleStride) -> per-final-partition capacities (estimate +
 // 8 sigma + 2% + 64) -> gapped partition-major layout: gcur = partBegin =
@@ -699,11 +701,16 @@ void scanExclusiveU32(const uint32_t *in, uint32_t *out, uint64_t n, uint32_t *t
 void scanExclusiveU32to64(const uint32_t *in, unsigned long long *out, uint64_t n, unsigned long long *total,
                           void *workspace, hipStream_t s);
 
-// Claim-scatter phase profile (partition.hip, built with
+// Claim-scatter phase profile (scatter_core.h, built with
 // -DHPCJOIN_SCATTER_PROF): shader-clock sums per tile phase [8], tiles [8],
-// ranges [9]; all zero in a normal build.
+// ranges [9]; all zero in a normal build.  Every scatter file is its own code
+// object with its own counters: scatterProfile() sums (and resets) them all
+// through the per-file scatterProfile*() below.
 void scatterProfile(unsigned long long out[10], bool reset);
 bool scatterProfileBuilt();
+void scatterProfileNet(unsigned long long acc[10], bool reset);
+void scatterProfileLocal(unsigned long long acc[10], bool reset);
+void scatterProfileAblation(unsigned long long acc[10], bool reset);
 
 // --------------------------------------------------- no-partitioning join
 uint64_t npjTableSlots(uint64_t innerSize);
@@ -783,7 +790,9 @@ void placeRows(const uint64_t *rows, const uint64_t *idx, uint64_t n, uint64_t *
 // first use of one of its kernels -- 1-2 ms each, which landed inside the
 // first join.  ExecContext calls this once per process and device: one
 // hipFuncGetAttributes per file loads them all up front.
-void preloadPartition();
+void preloadNetPartition();
+void preloadLocalPartition();
+void preloadScatterAblation();
 void preloadBuildProbe();
 void preloadKeyTables();
 void preloadBitmapJoin();
@@ -793,7 +802,9 @@ void preloadCollectives();
 void preloadMaterialize();
 void preloadDatagen();
 inline void preloadCodeObjects() {
-  preloadPartition();
+  preloadNetPartition();
+  preloadLocalPartition();
+  preloadScatterAblation();
   preloadBuildProbe();
   preloadKeyTables();
   preloadBitmapJoin();

@@ -183,7 +183,7 @@ void LocalPartitioning::partitionImpl(data::Window *w, int which) {
     }
     tl.beginAt("LPPART", p2);
     kernels::localScatter(w->getData(), wide, dItems, nItems, shift, bits, gcur, false, sout, ctx->stream(), gend,
-                          split, plan.localGeometry, frag, w->roundMap());
+                          split, frag, w->roundMap());
     tl.endAt("LPPART", tl.mark(ctx->stream()));
     kernels::claimOverflow(gcur, gend, P, overflowFlag[which], ctx->stream());
     // Read back with the join's final synchronisation (one flag per side).
@@ -224,7 +224,7 @@ void LocalPartitioning::partitionImpl(data::Window *w, int which) {
     tl.endAt("LPOFFSET", p2);
     tl.beginAt("LPPART", p2);
     kernels::localScatter(w->getData(), wide, dItems, nItems, shift, bits, gcur, narrow, out, ctx->stream(), nullptr,
-                          split, 0, frag, w->roundMap());
+                          split, frag, w->roundMap());
     tl.endAt("LPPART", tl.mark(ctx->stream()));
   } else {
     uint64_t *itemCursors = ctx->workspace().getArray<uint64_t>(std::max<uint64_t>(1, (uint64_t)nItems * F));

@@ -33,22 +33,19 @@ SampledNetworkPartitioning::~SampledNetworkPartitioning() = default;  // events 
 const SampledNetworkPartitioning::SidePlan &SampledNetworkPartitioning::sidePlan(uint64_t n) const {
   struct Key {
     uint64_t n;
-    uint32_t maxBlocks, bits, stride, ipt, nth, lp;
+    uint32_t maxBlocks, bits, stride, lp;
     bool operator<(const Key &o) const {
-      return std::tie(n, maxBlocks, bits, stride, ipt, nth, lp) <
-             std::tie(o.n, o.maxBlocks, o.bits, o.stride, o.ipt, o.nth, o.lp);
+      return std::tie(n, maxBlocks, bits, stride, lp) < std::tie(o.n, o.maxBlocks, o.bits, o.stride, o.lp);
     }
   };
   thread_local std::map<Key, SidePlan> cache;
   const uint32_t F = 1u << plan.networkBits;
-  const Key k{n, maxBlocks, plan.networkBits, sampleStride, plan.variants.netIpt, plan.variants.netThreads, roundLp()};
+  const Key k{n, maxBlocks, plan.networkBits, sampleStride, roundLp()};
   auto it = cache.find(k);
   if (it != cache.end()) return it->second;
   if (cache.size() > 64) cache.clear();
   SidePlan sp;
   sp.geom = kernels::partitionGeometry(n, maxBlocks);
-  sp.geom.ipt = plan.variants.netIpt;
-  sp.geom.nth = plan.variants.netThreads;
   sp.stride = kernels::sampleStrideFor(sp.geom, n, F, sampleStride);
   sp.sc = kernels::sampleScale(sp.geom, n, sp.stride, sp.stride == 1);
   sp.bound = kernels::sampledWindowCapacity(sp.sc, F, roundLp());

@@ -216,9 +216,7 @@ void SampledShuffle::scatterSide(int k) {
   const kernels::KeyMix mix{plan.keyMix ? 1u : 0u, plan.keyBits};
   Side &s = sides[k];
   const uint64_t n = s.relation->getLocalSize();
-  kernels::PartitionGeometry g = s.local->geometry();
-  g.ipt = plan.variants.netIpt;
-  g.nth = plan.variants.netThreads;
+  const kernels::PartitionGeometry &g = s.local->geometry();
   const uint32_t bpc = s.local->blocksPerChunk();
   const size_t perChunk = (size_t)G * F * (s.narrow ? 4 : 8);
   s.send = ctx->workspace().getArray<uint64_t>(std::max<uint64_t>(s.capTotal, 1));

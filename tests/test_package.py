@@ -62,6 +62,13 @@ def test_config_roundtrip(C, monkeypatch):
     assert d["network_bits"] == 7 and d["assignment"] == "ROUND_ROBIN" and d["materialize"] and d["format"] == "WIDE"
     monkeypatch.setenv("HPCJOIN_CHUNKS", "3")
     assert config_from_dict({}).chunks == 3
+    # retired scatter-geometry knobs are unknown fields, not silently accepted
+    with pytest.raises(KeyError):
+        config_from_dict({"net_ipt": 16})
+    with pytest.raises(KeyError):
+        config_from_dict({"local_geometry": 1})
+    d = config_to_dict(C.JoinConfig())
+    assert "net_ipt" not in d and "local_geometry" not in d
 
 
 def test_workload_presets(C):

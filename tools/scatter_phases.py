@@ -11,9 +11,11 @@ and the general path (random 63-bit keys: key-only network scatter + local
 split scatter, summed) and prints one JSON line per workload: each phase's
 share of wave 0's tile-loop cycles and its cycles per tile.
 
-Phases (partition.hip, ScatterProf): rank (includes waiting for the tile's
-loads), barrier A, claims + next-tile prefetch issue, scan, staging, write
-bases (the claim atomics land), barrier B, write-out issue.
+Phases (kernels/scatter_core.h, ScatterProf): rank (includes waiting for the
+tile's loads), barrier A, claims + next-tile prefetch issue, scan, staging,
+write bases (the claim atomics land), barrier B, write-out issue.  The network
+and the local scatter are separate code objects with counters of their own;
+ops.scatter_profile() returns their sum.
 """
 import argparse
 import json
