@@ -25,6 +25,7 @@
 #include "../utils/Fault.h"
 #include "../utils/Hip.h"
 #include "ProcessGroupCommunicator.h"
+#include "ScatterOps.h"
 
 namespace py = pybind11;
 using namespace hpcjoin;
@@ -1409,4 +1410,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       },
       py::arg("logical"), py::arg("lp"), py::arg("lv"), py::arg("lns"));
   ops.def("round_slots", &kernels::roundSlots, py::arg("max_cap"), py::arg("lp"), py::arg("lns"));
+  bindScatterOps(ops);
 }
