@@ -30,6 +30,7 @@ if native_available():
     KeyDistribution = _C.KeyDistribution
     AssignmentPolicy = _C.AssignmentPolicy
     TupleFormat = _C.TupleFormat
+    JoinKind = _C.JoinKind
     LocalCommunicator = _C.LocalCommunicator
     RcclCommunicator = _C.RcclCommunicator
     ProcessGroupCommunicator = _C.ProcessGroupCommunicator

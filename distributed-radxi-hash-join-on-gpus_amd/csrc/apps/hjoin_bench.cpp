@@ -6,7 +6,10 @@
 //               [--rank R --world W --id-file PATH]   (one process per GPU; rank 0
 //                                                      writes the ncclUniqueId to PATH)
 //               [--chunks C] [--net-bits B] [--local-bits B] [--materialize] [--wide]
-//               [--round-robin] [--perf-dir DIR]
+//               [--round-robin] [--perf-dir DIR] [--kind inner|semi|anti]
+// --kind semi|anti: `matches` is the number of outer tuples with / without an
+// inner partner; `correct` is checked against a host oracle computed here
+// when that is cheap (one rank, at most 64M tuples in all), else omitted.
 // Default workload per rank: 20M x 20M unique keys, as in main.cpp:70-71.
 #include <hip/hip_runtime.h>
 #include <unistd.h>
@@ -20,6 +23,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <unordered_set>
 #include <vector>
 
 #include "../comm/RcclCommunicator.h"
@@ -63,6 +67,16 @@ int main(int argc, char **argv) {
     else if (a == "--round-robin") cfg.assignment = core::AssignmentPolicy::RoundRobin;
     else if (a == "--two-level-only") cfg.bitmapJoin = false;  // no single-level bitmap join (N == 1)
     else if (a == "--perf-dir") perfDir = next();
+    else if (a == "--kind") {
+      const std::string k = next();
+      if (k == "inner") cfg.kind = core::JoinKind::Inner;
+      else if (k == "semi") cfg.kind = core::JoinKind::Semi;
+      else if (k == "anti") cfg.kind = core::JoinKind::Anti;
+      else {
+        std::fprintf(stderr, "unknown --kind %s (inner|semi|anti)\n", k.c_str());
+        return 2;
+      }
+    }
     else {
       std::fprintf(stderr, "unknown argument %s\n", a.c_str());
       return 2;
@@ -126,7 +140,23 @@ int main(int argc, char **argv) {
   data::Relation R(li, inner, loc, device), S(lo, outer, loc, device);
   R.generate(is, data::Relation::localOffsetFor(inner, rank, world));
   S.generate(os, data::Relation::localOffsetFor(outer, rank, world));
-  const uint64_t expected = data::Relation::expectedMatches(is, inner, os, outer);
+  uint64_t expected = data::Relation::expectedMatches(is, inner, os, outer);
+  if (cfg.kind != core::JoinKind::Inner) {
+    // Host oracle from the same generator specs: the outer tuples whose key is
+    // (semi) / is not (anti) among the inner keys.
+    expected = UINT64_MAX;
+    if (world == 1 && inner + outer <= (64ull << 20)) {
+      data::Relation Rh(inner, inner, Location::Host, 0), Sh(outer, outer, Location::Host, 0);
+      Rh.generate(is, 0);
+      Sh.generate(os, 0);
+      std::unordered_set<uint64_t> keys;
+      keys.reserve(2 * inner);
+      for (uint64_t i = 0; i < inner; ++i) keys.insert(Rh.getData()[i].key);
+      uint64_t semi = 0;
+      for (uint64_t i = 0; i < outer; ++i) semi += keys.count(Sh.getData()[i].key);
+      expected = cfg.kind == core::JoinKind::Semi ? semi : outer - semi;
+    }
+  }
 
   core::ExecContext ctx(loc, device, comm.get());
   operators::HashJoin join(&R, &S, &ctx, cfg);
@@ -149,10 +179,14 @@ int main(int argc, char **argv) {
   const double med = times.empty() ? 0 : times[times.size() / 2];
   if (rank == 0) {
     std::printf("{\"metric\": \"join_throughput\", \"value\": %.4f, \"unit\": \"billion tuples/s\", \"n_gpus\": %u, "
-                "\"ms_per_join\": %.3f, \"matches\": %lu, \"expected\": %s%lu, \"correct\": %s}\n",
-                med > 0 ? (inner + outer) / (med * 1e6) : 0.0, world, med, (unsigned long)matches,
-                expected == UINT64_MAX ? "-" : "", (unsigned long)(expected == UINT64_MAX ? 0 : expected),
-                (expected == UINT64_MAX || expected == matches) ? "true" : "false");
+                "\"ms_per_join\": %.3f, \"matches\": %lu",
+                med > 0 ? (inner + outer) / (med * 1e6) : 0.0, world, med, (unsigned long)matches);
+    if (cfg.kind != core::JoinKind::Inner) std::printf(", \"kind\": \"%s\"", core::joinKindName(cfg.kind));
+    if (cfg.kind == core::JoinKind::Inner || expected != UINT64_MAX)  // semi / anti without an oracle: omitted
+      std::printf(", \"expected\": %s%lu, \"correct\": %s", expected == UINT64_MAX ? "-" : "",
+                  (unsigned long)(expected == UINT64_MAX ? 0 : expected),
+                  (expected == UINT64_MAX || expected == matches) ? "true" : "false");
+    std::printf("}\n");
   }
   return (expected == UINT64_MAX || expected == matches) ? 0 : 1;
 }

@@ -13,6 +13,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <unordered_set>
 #include <vector>
 
 #include "../comm/InProcessCommunicator.h"
@@ -33,12 +34,15 @@ struct Case {
   bool wide, materialize, tpch;
   core::KeyHashing hashing;
   bool wire = false;  // bit-packed exchange (host twin of kernels/wire.hip)
+  core::JoinKind kind = core::JoinKind::Inner;  // semi / anti: outer rids, checked against a set oracle
 };
 
 bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
   auto group = std::make_shared<comm::InProcessGroup>(ranks);
   std::vector<std::string> errors(ranks);
   std::vector<uint64_t> matches(ranks, 0), pairs(ranks, 0);
+  std::vector<std::vector<uint64_t>> rids(ranks);
+  const bool inner = c.kind == core::JoinKind::Inner;
   data::GenSpec is, os;
   is.seed = 11;
   is.tpchSparse = c.tpch;
@@ -46,6 +50,11 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
   os.distribution = c.outer;
   os.domain = c.outer == kernels::KeyDistribution::Unique ? 0 : G;
   os.tpchSparse = c.tpch;
+  if (!inner) {  // repeated inner keys, and half of the outer key domain without a partner
+    is.distribution = kernels::KeyDistribution::Uniform;
+    is.domain = G / 4;
+    os.domain = 2 * G;
+  }
   const uint64_t GS = c.outer == kernels::KeyDistribution::Unique ? G : 3 * G;
   auto rankMain = [&](uint32_t r) {
     try {
@@ -58,6 +67,7 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
       core::JoinConfig cfg;
       cfg.format = c.wide ? core::TupleFormat::Wide : core::TupleFormat::Compressed;
       cfg.materialize = c.materialize;
+      cfg.kind = c.kind;
       cfg.keyHashing = c.hashing;
       cfg.chunks = 2;
       cfg.wireCodec = c.wire ? core::WireCodecMode::On : core::WireCodecMode::Off;
@@ -65,7 +75,8 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
       operators::JoinResult res = j.run();
       matches[r] = res.globalMatches;
       pairs[r] = res.outputPairs;
-      if (c.materialize) {  // fetch 32-byte payload rows of both sides from their owners
+      if (!inner && c.materialize) rids[r].assign(j.getOutputRids(), j.getOutputRids() + res.outputRids);
+      if (inner && c.materialize) {  // fetch 32-byte payload rows of both sides from their owners
         const uint64_t oR = data::Relation::localOffsetFor(G, r, ranks), oS = data::Relation::localOffsetFor(GS, r, ranks);
         std::vector<uint64_t> rowsR(R.getLocalSize() * kernels::ROW_WORDS), rowsS(S.getLocalSize() * kernels::ROW_WORDS);
         for (uint64_t i = 0; i < R.getLocalSize(); ++i)
@@ -90,7 +101,18 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
   std::vector<std::thread> ts;
   for (uint32_t r = 0; r < ranks; ++r) ts.emplace_back(rankMain, r);
   for (auto &t : ts) t.join();
-  const uint64_t expected = data::Relation::expectedMatches(is, G, os, GS);
+  uint64_t expected = data::Relation::expectedMatches(is, G, os, GS);
+  std::unordered_set<uint64_t> expectedRids;
+  if (!inner) {  // the outer tuples whose key is (semi) / is not (anti) among the inner keys
+    data::Relation R(G, G, Location::Host, 0), S(GS, GS, Location::Host, 0);
+    R.generate(is, 0);
+    S.generate(os, 0);
+    std::unordered_set<uint64_t> keys;
+    for (uint64_t i = 0; i < G; ++i) keys.insert(R.getData()[i].key);
+    for (uint64_t i = 0; i < GS; ++i)
+      if ((keys.count(S.getData()[i].key) != 0) == (c.kind == core::JoinKind::Semi)) expectedRids.insert(S.getData()[i].rid);
+    expected = expectedRids.size();
+  }
   bool ok = true;
   for (uint32_t r = 0; r < ranks; ++r) {
     if (!errors[r].empty()) {
@@ -102,7 +124,16 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
       ok = false;
     }
   }
-  if (ok && c.materialize) {
+  if (ok && c.materialize && !inner) {  // the ranks' rid lists together: the oracle set, no rid twice
+    std::unordered_set<uint64_t> seen;
+    for (const auto &v : rids)
+      for (uint64_t x : v)
+        if (!expectedRids.count(x) || !seen.insert(x).second) ok = false;
+    if (seen.size() != expected) ok = false;
+    if (!ok) std::printf("[%s] rid lists differ from the oracle (%lu distinct, expected %lu)\n", c.name,
+                         (unsigned long)seen.size(), (unsigned long)expected);
+  }
+  if (ok && c.materialize && inner) {
     uint64_t total = 0;
     for (uint64_t p : pairs) total += p;
     if (total != expected) {
@@ -161,6 +192,10 @@ int main(int argc, char **argv) {
       {"mix_on_wide", kernels::KeyDistribution::Modulo, true, false, false, core::KeyHashing::On},
       {"wire_zipf", kernels::KeyDistribution::Zipf, false, false, false, core::KeyHashing::Auto, true},
       {"wire_tpch_materialize", kernels::KeyDistribution::Modulo, false, true, true, core::KeyHashing::Auto, true},
+      {"semi_zipf_materialize", kernels::KeyDistribution::Zipf, false, true, false, core::KeyHashing::Auto, true,
+       core::JoinKind::Semi},
+      {"anti_wide_materialize", kernels::KeyDistribution::Uniform, true, true, false, core::KeyHashing::Auto, false,
+       core::JoinKind::Anti},
   };
   bool ok = true;
   for (const Case &c : cases) ok = runCase(c, ranks, G) && ok;

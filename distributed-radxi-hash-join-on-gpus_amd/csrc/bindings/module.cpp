@@ -237,6 +237,97 @@ py::dict opBuildProbe(const at::Tensor &R, const at::Tensor &S, const at::Tensor
   return d;
 }
 
+// ---- semi / anti join over partition-major inputs: mark, count, place ------
+// marks: bool per outer position; semi_count; semi_rids / anti_rids: the outer
+// rids the compaction emits for either kind (kernels/semi_join.hip and the
+// host twins).
+py::dict opBuildProbeMarks(const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR, const at::Tensor &partS,
+                           int64_t fragShift, int64_t keyShift, bool wide, int64_t rChunk, int64_t sChunk) {
+  TORCH_CHECK(R.device() == S.device(), "R and S must live on the same device");
+  TORCH_CHECK(rChunk >= 1 && sChunk >= 1, "r_chunk and s_chunk must be positive");
+  setDevice(R);
+  kernels::BPArgs a;
+  a.R = R.data_ptr();
+  a.S = S.data_ptr();
+  at::Tensor pr = partR.to(R.device()).contiguous(), ps = partS.to(R.device()).contiguous();
+  TORCH_CHECK(pr.size(0) == ps.size(0) && pr.size(0) >= 1, "part_r and part_s must have the same P + 1 entries");
+  a.partR = ptr<uint64_t>(pr);
+  a.partS = ptr<uint64_t>(ps);
+  a.P = (uint32_t)pr.size(0) - 1;
+  a.rChunk = (uint32_t)rChunk;
+  a.sChunk = (uint32_t)sChunk;
+  a.fragShift = (uint32_t)fragShift;
+  a.keyShift = (uint32_t)keyShift;
+  a.wide = wide;
+  const int64_t n = S.size(0);
+  const int64_t words = (int64_t)kernels::markWords((uint64_t)n);
+  at::Tensor marks = at::zeros({words}, like(R));
+  at::Tensor rids[2] = {at::empty({n + 1}, like(R)), at::empty({n + 1}, like(R))};
+  uint64_t count[2] = {0, 0};
+  if (R.is_cuda()) {
+    at::Tensor ctr = at::zeros({4}, like(R));
+    a.result = reinterpret_cast<unsigned long long *>(ctr.data_ptr());
+    a.outCursor = a.result + 1;
+    uint32_t *nItems = reinterpret_cast<uint32_t *>(a.result + 2), *nUnits = reinterpret_cast<uint32_t *>(a.result + 3);
+    const int64_t P1 = std::max<int64_t>(a.P, 1);
+    at::Tensor counts = at::empty({P1}, like(R, at::kInt)), offsets = at::empty({P1}, like(R, at::kInt));
+    const uint32_t unitCap = a.P + (uint32_t)(n / sChunk) + 1;
+    at::Tensor scanWs = at::empty({(int64_t)kernels::scanWorkspaceBytes(std::max<uint64_t>(a.P, unitCap)) / 4 + 1},
+                                  like(R, at::kInt));
+    uint32_t capacity = 2 * a.P + (uint32_t)(n / a.sChunk + R.size(0) / a.rChunk) + 1024;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      at::Tensor items = at::empty({(int64_t)capacity * 2}, like(R));
+      ctr.zero_();
+      marks.zero_();
+      kernels::bpPlanCounts(a, ptr<uint32_t>(counts), nullptr);
+      kernels::scanExclusiveU32(ptr<uint32_t>(counts), ptr<uint32_t>(offsets), a.P, nItems, scanWs.data_ptr(), nullptr);
+      kernels::bpEmit(a, ptr<uint32_t>(counts), ptr<uint32_t>(offsets), ptr<kernels::BPItem>(items), capacity, nullptr);
+      kernels::bpMark(a, ptr<kernels::BPItem>(items), nItems, capacity, ptr<unsigned long long>(marks), nullptr);
+      HIP_CHECK(hipDeviceSynchronize());
+      const uint32_t need = (uint32_t)(ctr.cpu()[2].item<int64_t>() & 0xFFFFFFFF);
+      if (need <= capacity) break;
+      TORCH_CHECK(attempt == 0, "build_probe_marks: the work-item list overflowed twice");
+      capacity = need;
+    }
+    at::Tensor units = at::empty({(int64_t)unitCap}, like(R));
+    at::Tensor unitCounts = at::empty({(int64_t)unitCap}, like(R, at::kInt));
+    at::Tensor unitOffsets = at::empty({(int64_t)unitCap}, like(R));
+    kernels::markPlanUnits(a, ptr<uint32_t>(counts), nullptr);
+    kernels::scanExclusiveU32(ptr<uint32_t>(counts), ptr<uint32_t>(offsets), a.P, nUnits, scanWs.data_ptr(), nullptr);
+    kernels::markEmitUnits(a, ptr<uint32_t>(counts), ptr<uint32_t>(offsets), ptr<kernels::MarkUnit>(units), unitCap,
+                           nullptr);
+    for (int anti = 0; anti < 2; ++anti) {
+      ctr.slice(0, 0, 2).zero_();
+      unitCounts.zero_();
+      kernels::markCount(a, ptr<kernels::MarkUnit>(units), nUnits, unitCap, ptr<unsigned long long>(marks), anti != 0,
+                         ptr<uint32_t>(unitCounts), nullptr);
+      kernels::scanExclusiveU32to64(ptr<uint32_t>(unitCounts), ptr<unsigned long long>(unitOffsets), unitCap,
+                                    a.outCursor, scanWs.data_ptr(), nullptr);
+      kernels::markPlace(a, ptr<kernels::MarkUnit>(units), nUnits, unitCap, ptr<unsigned long long>(marks), anti != 0,
+                         ptr<unsigned long long>(unitOffsets), ptr<unsigned long long>(rids[anti]), (uint64_t)n,
+                         nullptr);
+      HIP_CHECK(hipDeviceSynchronize());
+      at::Tensor h = ctr.cpu();
+      count[anti] = (uint64_t)h[0].item<int64_t>();
+      TORCH_CHECK((uint64_t)h[1].item<int64_t>() == count[anti], "build_probe_marks: count and place passes disagree");
+    }
+  } else {
+    host::buildProbeMark(a, ptr<uint64_t>(marks));
+    for (int anti = 0; anti < 2; ++anti)
+      count[anti] = host::markCompact(a, ptr<uint64_t>(marks), anti != 0, ptr<uint64_t>(rids[anti]), (uint64_t)n);
+  }
+  at::Tensor pos = at::arange(n, like(R));
+  at::Tensor bits = at::bitwise_and(
+      at::bitwise_right_shift(marks.index_select(0, at::bitwise_right_shift(pos, 6)), at::bitwise_and(pos, 63)), 1);
+  py::dict d;
+  d["marks"] = bits.to(at::kBool);
+  d["semi_count"] = count[0];
+  d["anti_count"] = count[1];
+  d["semi_rids"] = rids[0].narrow(0, 0, (int64_t)count[0]);
+  d["anti_rids"] = rids[1].narrow(0, 0, (int64_t)count[1]);
+  return d;
+}
+
 at::Tensor opGenerate(int64_t n, int64_t globalOffset, int64_t globalSize, const data::GenSpec &spec,
                       const std::string &device) {
   at::Tensor out = at::empty({n, 2}, at::TensorOptions().dtype(at::kLong).device(device));
@@ -561,6 +652,7 @@ py::dict resultToDict(const operators::JoinResult &r) {
   d["local_matches"] = r.localMatches;
   d["global_matches"] = r.globalMatches;
   d["output_pairs"] = r.outputPairs;
+  d["output_rids"] = r.outputRids;
   d["output_overflow"] = r.outputOverflow;
   d["rows_fused"] = r.rowsFused;
   d["split_partitions"] = r.splitPartitions;
@@ -676,8 +768,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   py::enum_<core::ExchangeMode>(m, "ExchangeMode")
       .value("RCCL", core::ExchangeMode::Rccl)
       .value("ONE_SIDED", core::ExchangeMode::OneSided);
+  py::enum_<core::JoinKind>(m, "JoinKind")
+      .value("INNER", core::JoinKind::Inner)
+      .value("SEMI", core::JoinKind::Semi)
+      .value("ANTI", core::JoinKind::Anti);
   py::class_<core::JoinConfig>(m, "JoinConfig")
       .def(py::init<>())
+      .def_readwrite("kind", &core::JoinConfig::kind)
       .def_readwrite("network_bits", &core::JoinConfig::networkBits)
       .def_readwrite("local_bits", &core::JoinConfig::localBits)
       .def_readwrite("two_level", &core::JoinConfig::twoLevel)
@@ -769,6 +866,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readonly("two_level", &core::JoinPlan::twoLevel)
       .def_readonly("wide", &core::JoinPlan::wide)
       .def_readonly("materialize", &core::JoinPlan::materialize)
+      .def_readonly("kind", &core::JoinPlan::kind)
       .def("__repr__", &core::JoinPlan::describe);
   m.def("make_plan", &core::makePlan, py::arg("config"), py::arg("number_of_nodes"), py::arg("global_inner"),
         py::arg("global_outer"), py::arg("max_key"), py::arg("max_rid"));
@@ -1089,6 +1187,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
             // Collective.  Returns [pairs, 10] int64: rid_inner, rid_outer, inner row (4), outer row (4)
             // (return_stats: (rows, phase times and link bytes of the request/response exchange)).
             TORCH_CHECK(j.getConfig().materialize, "join was not run with materialize=True");
+            TORCH_CHECK(j.getConfig().kind == core::JoinKind::Inner,
+                        "materialize_payloads needs kind=INNER: a kind=SEMI / ANTI join has outer rids "
+                        "(output_rids()), not pairs");
             TORCH_CHECK(!j.lastResult().rowsFused, "the last run wrote rows directly (join_materialized)");
             TORCH_CHECK(innerRows.dim() == 2 && innerRows.size(1) == (int64_t)kernels::ROW_WORDS &&
                             outerRows.dim() == 2 && outerRows.size(1) == (int64_t)kernels::ROW_WORDS,
@@ -1123,6 +1224,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
             // N = 1 write the rows from the build/probe's materialize pass
             // (no pair array); otherwise run() + LateMaterialization.
             TORCH_CHECK(j.getConfig().materialize, "join_materialized needs materialize=True");
+            TORCH_CHECK(j.getConfig().kind == core::JoinKind::Inner,
+                        "join_materialized cannot be combined with kind=SEMI / ANTI: such a join has outer rids "
+                        "(output_rids()), not (inner, outer) pairs to fetch rows for");
             TORCH_CHECK(innerRows.dim() == 2 && innerRows.size(1) == (int64_t)kernels::ROW_WORDS &&
                             outerRows.dim() == 2 && outerRows.size(1) == (int64_t)kernels::ROW_WORDS,
                         "payload rows must be [n, 4] int64 (32 bytes)");
@@ -1194,6 +1298,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
             HIP_CHECK(hipMemcpy(out.data_ptr(), j.getOutput(), n * 16, hipMemcpyDefault));
           else
             std::memcpy(out.data_ptr(), j.getOutput(), n * 16);
+        }
+        return out;
+      })
+      .def("output_rids", [](operators::HashJoin &j) {
+        // kind = SEMI / ANTI with materialize: the qualifying outer rids, int64 [m], any order.
+        const uint64_t n = j.lastResult().outputRids;
+        at::Tensor out = at::empty({(int64_t)n}, at::kLong);
+        if (n && j.getOutputRids()) {
+          HJ_CHECK(j.outputRidsValid(),
+                   "HashJoin.output_rids(): the rids of the last run were in the engine workspace, which a later "
+                   "join, plan or trim_workspace on the same context has since reused; read output_rids() right "
+                   "after run()");
+          if (j.context()->onDevice())
+            HIP_CHECK(hipMemcpy(out.data_ptr(), j.getOutputRids(), n * 8, hipMemcpyDefault));
+          else
+            std::memcpy(out.data_ptr(), j.getOutputRids(), n * 8);
         }
         return out;
       });
@@ -1277,6 +1397,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   ops.def("build_probe", &opBuildProbe, py::arg("R"), py::arg("S"), py::arg("part_r"), py::arg("part_s"),
           py::arg("frag_shift"), py::arg("key_shift"), py::arg("wide") = false, py::arg("materialize") = false,
           py::arg("r_chunk") = 4096, py::arg("s_chunk") = 65536, py::arg("out_capacity") = 0);
+  ops.def("build_probe_marks", &opBuildProbeMarks, py::arg("R"), py::arg("S"), py::arg("part_r"), py::arg("part_s"),
+          py::arg("frag_shift"), py::arg("key_shift"), py::arg("wide") = false, py::arg("r_chunk") = 4096,
+          py::arg("s_chunk") = 65536);
   ops.def("generate", &opGenerate, py::arg("n"), py::arg("global_offset"), py::arg("global_size"), py::arg("spec"),
           py::arg("device") = "cpu");
   ops.def("scan_u32", &opScan);

@@ -9,24 +9,26 @@ namespace core {
 
 std::string JoinConfig::describe() const {
   return utils::format("JoinConfig(networkBits=%u localBits=%u twoLevel=%d keyShift=%u assignment=%s format=%s "
-                       "materialize=%d buildTarget=%lu rChunk=%u sChunk=%u chunks=%u)",
+                       "materialize=%d buildTarget=%lu rChunk=%u sChunk=%u chunks=%u%s%s)",
                        networkBits, localBits, (int)twoLevel, keyShift,
                        assignment == AssignmentPolicy::LPT ? "lpt" : "round_robin",
                        format == TupleFormat::Wide ? "wide" : "compressed", (int)materialize,
-                       (unsigned long)buildTarget, rChunk, sChunk, chunks);
+                       (unsigned long)buildTarget, rChunk, sChunk, chunks, kind == JoinKind::Inner ? "" : " kind=",
+                       kind == JoinKind::Inner ? "" : joinKindName(kind));
 }
 
 std::string JoinPlan::describe() const {
   return utils::format("JoinPlan(nodes=%u networkBits=%u localBits=%u twoLevel=%d keyShift=%u fragShift=%u "
                        "rChunk=%u sChunk=%u chunks=%u wide=%d materialize=%d keyMix=%d sampled=%d assignment=%s wire=%u/%u "
-                       "split=%d splitHist=%d pipeOuter=%d bitmap=%d/%u%s%s%s%s%s)",
+                       "split=%d splitHist=%d pipeOuter=%d bitmap=%d/%u%s%s%s%s%s%s%s)",
                        numberOfNodes, networkBits, localBits, (int)twoLevel, keyShift, fragShift, rChunk, sChunk,
                        chunks, (int)wide, (int)materialize, (int)keyMix, (int)sampledNetwork,
                        assignment == AssignmentPolicy::LPT ? "lpt" : "round_robin", wireBits[0], wireBits[1],
                        (int)splitLocal, (int)splitHistogram, (int)pipelineOuter, (int)bitmapJoin, bitmapBits,
                        bitmapReplicated ? " replicated" : "", keyOnly ? " keyOnly" : "",
                        oneSided ? " oneSided" : "", fragments && !bitmapJoin ? " fragments" : "",
-                       innerRepeats ? " innerRepeats" : "");
+                       innerRepeats ? " innerRepeats" : "", kind == JoinKind::Inner ? "" : " kind=",
+                       kind == JoinKind::Inner ? "" : joinKindName(kind));
 }
 
 JoinPlan makePlan(const JoinConfig &cfg, uint32_t numberOfNodes, uint64_t globalInner, uint64_t globalOuter,
@@ -36,11 +38,13 @@ JoinPlan makePlan(const JoinConfig &cfg, uint32_t numberOfNodes, uint64_t global
   p.twoLevel = cfg.twoLevel;
   p.wide = cfg.format == TupleFormat::Wide;
   p.materialize = cfg.materialize;
+  p.kind = cfg.kind;
   p.directCount = cfg.directCount;
   p.localItemTiles = std::max<uint32_t>(1, std::min<uint32_t>(cfg.localItemTiles, 1024));
   p.variants = cfg.variants;
   p.assignment = cfg.assignment;
-  p.skewSplit = cfg.skewSplit && cfg.assignment == AssignmentPolicy::LPT && numberOfNodes > 1;
+  p.skewSplit = cfg.skewSplit && cfg.assignment == AssignmentPolicy::LPT && numberOfNodes > 1 &&
+                cfg.kind == JoinKind::Inner;  // (JoinConfig::skewSplit: a replicated outer tuple would be marked twice)
   p.chunks = std::max<uint32_t>(1, cfg.chunks);
   p.localHistogram = cfg.localHistogram;
   p.sampleStride = std::max<uint32_t>(1, cfg.sampleStride);
@@ -55,7 +59,9 @@ JoinPlan makePlan(const JoinConfig &cfg, uint32_t numberOfNodes, uint64_t global
   // is 1024: with their 32-byte payload rows (32 KiB) they fit the LDS of the
   // fused row-output kernel, 3 workgroups per CU (kernels/build_probe.hip,
   // bpMatRowsKernel).  SF100: 35.6 ms fused vs 42.0 ms join + separate pass.
-  const bool matNarrow = p.materialize && !p.wide && !cfg.rChunk;
+  // (Semi / anti joins keep keys only in LDS: sized as counting joins.)
+  const bool pairs = p.materialize && p.kind == JoinKind::Inner;
+  const bool matNarrow = pairs && !p.wide && !cfg.rChunk;
   const uint32_t matTarget = numberOfNodes == 1 ? 1024 : 2048;
   // >= 8 network partitions per node so LPT has room to balance.
   const uint32_t minNet = std::max<uint32_t>(4, ceilLog2(numberOfNodes) + 3);
@@ -95,7 +101,7 @@ JoinPlan makePlan(const JoinConfig &cfg, uint32_t numberOfNodes, uint64_t global
     const uint32_t high = keyBits > p.networkBits ? keyBits - p.networkBits : 0;
     const uint32_t local = p.twoLevel ? p.localBits : 0;
     if (ks >= 64 || high > 64 - ks || high > 31 + local) {
-      if (p.materialize)
+      if (p.carriesRids())
         p.wide = true;
       else
         p.keyOnly = true;
@@ -142,7 +148,7 @@ JoinPlan makePlan(const JoinConfig &cfg, uint32_t numberOfNodes, uint64_t global
   if (cfg.rChunk) {
     p.rChunk = cfg.rChunk;
   } else {
-    const uint32_t entry = p.wide ? (p.materialize ? 16 : 8) : (p.materialize || p.keyOnly ? 8 : 4);
+    const uint32_t entry = p.wide ? (pairs ? 16 : 8) : (pairs || p.keyOnly ? 8 : 4);
     const uint32_t budget = (entry == 4 || p.keyOnly) ? 32 * 1024 : matNarrow ? 16 * matTarget : 64 * 1024;
     p.rChunk = (budget / entry) / 2;
   }

@@ -66,7 +66,21 @@ enum class ExchangeMode : int {
                  // (IPC-mapped peer allocations; plain pointers for in-process ranks), then a barrier
 };
 
+// What a join answers about R |x| S.  Semi: the outer tuples with at least one
+// inner partner; Anti: those with none.  Each qualifying outer tuple counts,
+// and is emitted, exactly once however many inner copies its key has
+// (kernels/semi_join.hip: mark, then compact).
+enum class JoinKind : int { Inner = 0, Semi = 1, Anti = 2 };
+inline const char *joinKindName(JoinKind k) {
+  return k == JoinKind::Semi ? "semi" : k == JoinKind::Anti ? "anti" : "inner";
+}
+
 struct JoinConfig {
+  // Semi / Anti: local_matches / global_matches count the qualifying outer
+  // tuples, and with materialize the output is a list of outer rids
+  // (HashJoin::getOutputRids) instead of pairs.  Not combined with outputHost,
+  // a RowSink, or a materializing capacity spill.
+  JoinKind kind = JoinKind::Inner;
   uint32_t networkBits = 0;   // radix bits of the network pass (0 = auto)
   uint32_t localBits = 0;     // radix bits of the local pass (0 = auto; ignored if !twoLevel)
   bool twoLevel = true;       // run the local (second) partitioning pass
@@ -107,7 +121,9 @@ struct JoinConfig {
   bool splitLocal = true;       // device: split local pass output (u32 rid + u16 fragment columns) when they fit
   // N > 1, LPT: a network partition above one rank's fair share of |R| + |S|
   // is joined by several ranks (larger side divided, smaller replicated;
-  // histograms/AssignmentMap).
+  // histograms/AssignmentMap).  Forced off for kind != Inner: a hot partition
+  // joined by several ranks may divide its inner side and replicate its outer
+  // side, which would mark one outer tuple on several ranks.
   bool skewSplit = true;
   bool directCount = true;      // count-only build/probe: direct-addressed LDS counts when fragments are <= 13 bits
   bool splitHistogram = true;   // N > 1 on device: outer exact histogram overlaps the inner exchange
@@ -170,6 +186,12 @@ struct JoinPlan {
   bool twoLevel = true;
   bool wide = false;
   bool materialize = false;
+  JoinKind kind = JoinKind::Inner;
+  // The tuples keep their rids through both passes and one BuildProbe sees
+  // whole partitions: materializing joins, and semi / anti joins (whose
+  // result is per outer tuple).  Rules out the rid-free layouts (keyOnly,
+  // fragments), the bitmap plans and the pipelined outer side.
+  bool carriesRids() const { return materialize || kind != JoinKind::Inner; }
   bool keyMix = false;        // radix digits from kernels::KeyMix{keyBits} of the key
   // Counting join whose keys do not fit a CompressedTuple (sparse 63-bit keys):
   // after the network pass a tuple is the 8-byte word key >> networkBits (no

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstring>
 #include <unordered_map>
+#include <unordered_set>
 
 #include "../utils/Debug.h"
 
@@ -241,6 +242,45 @@ uint64_t buildProbe(const kernels::BPArgs &a) {
     }
   }
   return matches;
+}
+
+void buildProbeMark(const kernels::BPArgs &a, uint64_t *marks) {
+  std::unordered_set<uint64_t> keys;
+  for (uint32_t p = 0; p < a.P; ++p) {
+    const uint64_t rb = a.partR[p], re = a.partREnd ? a.partREnd[p] : a.partR[p + 1], sb = a.partS[p],
+                   se = a.partSEnd ? a.partSEnd[p] : a.partS[p + 1];
+    if (re == rb || se == sb) continue;
+    keys.clear();
+    keys.reserve(2 * (re - rb));
+    if (!a.wide) {
+      const uint64_t *R = static_cast<const uint64_t *>(a.R), *S = static_cast<const uint64_t *>(a.S);
+      for (uint64_t t = rb; t < re; ++t) keys.insert(a.keyShift >= 64 ? 0 : R[t] >> a.keyShift);
+      for (uint64_t s = sb; s < se; ++s)
+        if (keys.count(a.keyShift >= 64 ? 0 : S[s] >> a.keyShift)) marks[s >> 6] |= 1ull << (s & 63);
+    } else {
+      const data::Tuple *R = static_cast<const data::Tuple *>(a.R), *S = static_cast<const data::Tuple *>(a.S);
+      for (uint64_t t = rb; t < re; ++t) keys.insert(R[t].key);
+      for (uint64_t s = sb; s < se; ++s)
+        if (keys.count(S[s].key)) marks[s >> 6] |= 1ull << (s & 63);
+    }
+  }
+}
+
+uint64_t markCompact(const kernels::BPArgs &a, const uint64_t *marks, bool anti, uint64_t *out,
+                     uint64_t outCapacity) {
+  const uint64_t ridMask = a.keyShift >= 64 ? ~0ull : ((1ull << a.keyShift) - 1);
+  uint64_t n = 0;
+  for (uint32_t p = 0; p < a.P; ++p) {
+    const uint64_t sb = a.partS[p], se = a.partSEnd ? a.partSEnd[p] : a.partS[p + 1];
+    for (uint64_t s = sb; s < se; ++s) {
+      const bool marked = (marks[s >> 6] >> (s & 63)) & 1;
+      if (marked == anti) continue;
+      if (out && n < outCapacity)
+        out[n] = a.wide ? static_cast<const data::Tuple *>(a.S)[s].rid : (static_cast<const uint64_t *>(a.S)[s] & ridMask);
+      ++n;
+    }
+  }
+  return n;
 }
 
 uint64_t npjJoin(const data::Tuple *R, uint64_t nR, const data::Tuple *S, uint64_t nS) {

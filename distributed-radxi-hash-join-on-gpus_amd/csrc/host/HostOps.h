@@ -40,6 +40,13 @@ void localScatter(const void *in, bool wide, const kernels::LocalItem *items, ui
 // Bucket-chained build/probe per final partition; returns matches and (when
 // a.materialize) writes pairs through a.outPairs / a.outCursor (host memory).
 uint64_t buildProbe(const kernels::BPArgs &a);
+// Semi / anti joins (twins of kernels/semi_join.hip).  The host walks whole
+// partitions: buildProbeMark sets bit s of marks for every outer position s
+// whose key occurs on the inner side of its partition; markCompact counts the
+// marked (anti: unmarked) positions of the partitions' valid ranges and, with
+// out != null, appends their rids (at most outCapacity are written).
+void buildProbeMark(const kernels::BPArgs &a, uint64_t *marks);
+uint64_t markCompact(const kernels::BPArgs &a, const uint64_t *marks, bool anti, uint64_t *out, uint64_t outCapacity);
 
 // Wire codec (kernels.h, WireCodec) over host segment lists.
 void wirePack(const uint64_t *raw, uint64_t *wire, const kernels::WireSeg *segs, uint32_t nSegs,

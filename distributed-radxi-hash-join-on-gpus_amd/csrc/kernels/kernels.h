@@ -495,6 +495,42 @@ void bpKeyDedupMerge(const BPArgs &a, uint32_t maxParts, hipStream_t s);
 constexpr uint32_t BP_DEDUP_SEGS = 16;
 constexpr uint64_t BP_DEDUP_SEG_MIN = 32768;
 
+// Semi- and anti-joins (semi_join.hip; core::JoinKind): mark, then compact.
+// marks: one bit per position of the partitioned outer buffer (markWords(n)
+// u64 words for n positions, zeroed by the caller before bpMark).
+struct MarkUnit {   // one run of a.sChunk positions of one final partition's outer tuples
+  uint32_t part;
+  uint32_t chunk;
+};
+// Unit size of the engine's compaction (BuildProbe passes min(sChunk,
+// MARK_UNIT) as a.sChunk to the unit kernels): one wave walks a unit, so with
+// skewed outer keys 65536-position units of hot partitions left a long tail.
+// MI355X, 128M x 128M, Zipf(0.75) outer keys, semi-join build/probe span:
+// 1.44 ms at 65536, 1.23 at 16384, 1.19 at 8192, 1.15 at 4096, 1.18 at 2048
+// (unique outer keys: 0.98-1.00 ms at every size).
+constexpr uint32_t MARK_UNIT = 4096;
+size_t bpMarkLdsBytes(const BPArgs &a);
+uint64_t markWords(uint64_t positions);
+// Over the BPItem list of bpPlanCounts / bpEmit: builds each item's inner keys
+// as a set in LDS and ORs the hit masks of its outer tuples into marks.
+// Layouts: CompressedTuples, split columns, wide tuples (not key-only words).
+void bpMark(const BPArgs &a, const BPItem *items, const uint32_t *nItems, uint32_t capacity,
+            unsigned long long *marks, hipStream_t s);
+// Outer units: counts[p] = units of partition p (every partition with outer
+// tuples, also those without inner ones); after a scan, markEmitUnits lists
+// them.  There are at most P + outer tuples / a.sChunk units.
+void markPlanUnits(const BPArgs &a, uint32_t *counts, hipStream_t s);
+void markEmitUnits(const BPArgs &a, const uint32_t *counts, const uint32_t *offsets, MarkUnit *units,
+                   uint32_t capacity, hipStream_t s);
+// unitCounts[u] = marked (anti: unmarked) tuples of unit u; their sum is added
+// to *a.result (one atomic per workgroup).
+void markCount(const BPArgs &a, const MarkUnit *units, const uint32_t *nUnits, uint32_t capacity,
+               const unsigned long long *marks, bool anti, uint32_t *unitCounts, hipStream_t s);
+// out[unitOffsets[u] ...] = rids of unit u's marked (anti: unmarked) tuples, in position order.
+void markPlace(const BPArgs &a, const MarkUnit *units, const uint32_t *nUnits, uint32_t capacity,
+               const unsigned long long *marks, bool anti, const unsigned long long *unitOffsets,
+               unsigned long long *out, uint64_t outCapacity, hipStream_t s);
+
 // Single-level counting join of unique inner keys (bitmap_join.hip): one
 // workgroup per network partition sets a 2^bits LDS bitmap from the inner
 // fragments and tests the outer ones.
@@ -795,6 +831,7 @@ void preloadLocalPartition();
 void preloadScatterAblation();
 void preloadBuildProbe();
 void preloadKeyTables();
+void preloadSemiJoin();
 void preloadBitmapJoin();
 void preloadScan();
 void preloadWire();
@@ -807,6 +844,7 @@ inline void preloadCodeObjects() {
   preloadScatterAblation();
   preloadBuildProbe();
   preloadKeyTables();
+  preloadSemiJoin();
   preloadBitmapJoin();
   preloadScan();
   preloadWire();

@@ -115,6 +115,10 @@ void HashJoin::planPasses() {
   K = agreeMax(K);
   passes = K;
   if (K == 1) return;
+  JOIN_ASSERT(!plan.materialize || plan.kind == core::JoinKind::Inner, "HashJoin",
+              "capacity spill (%u passes) of a materializing JoinConfig.kind = %s join is not supported: the rid list "
+              "lives in the workspace; count-only semi- and anti-joins do spill",
+              K, core::joinKindName(plan.kind));
   JOIN_ASSERT(!plan.materialize || config.outputHost, "HashJoin",
               "capacity spill (%u passes) of a materializing join needs JoinConfig.outputHost: the pairs of every "
               "pass go to one pinned host buffer",
@@ -269,6 +273,7 @@ JoinResult HashJoin::runPasses() {
   total.joinMs = (nowUs() - t0) / 1000.0;
   total.networkMs = total.joinMs;
   result = total;
+  outputRids = nullptr;  // count-only: the pass joins' rid lists (if any) are gone with their workspace
   if (plan.materialize) {  // every pass appended to the caller's host buffer
     output = static_cast<const ulonglong2 *>(config.outputHost);
     outputEpoch = ctx->workspace().epoch();
@@ -285,6 +290,10 @@ void HashJoin::makeJoinPlan() {
   };
   JOIN_ASSERT(usable(innerRelation) && usable(outerRelation), "HashJoin",
               "relations must live where the engine runs (%s) or in pinned host memory", locationName(ctx->location()));
+  JOIN_ASSERT(config.kind == core::JoinKind::Inner || !config.outputHost, "HashJoin",
+              "JoinConfig.kind = %s cannot be combined with JoinConfig.outputHost (output_host): a semi- or anti-join "
+              "writes outer rids to the workspace, not pairs to a host buffer",
+              core::joinKindName(config.kind));
   // Max key / rid over both relations and all ranks (the plan must be identical
   // everywhere), plus each rank's rid range per relation and exchange chunk
   // (wire codec bases).  Per rank: {max key, max rid, then for inner and outer
@@ -385,13 +394,13 @@ void HashJoin::makeJoinPlan() {
   // fragment column alone (4 + 2 bytes per tuple instead of 8 + 6).
   // No rid travels, so the rid width (which decides splitLocal) does not
   // matter: only that the u16 column holds the fragment above both digits.
-  plan.fragments = plan.sampledNetwork && !plan.materialize && !plan.wide && !plan.keyOnly && plan.twoLevel &&
+  plan.fragments = plan.sampledNetwork && !plan.carriesRids() && !plan.wide && !plan.keyOnly && plan.twoLevel &&
                    plan.keyBits <= plan.networkBits + plan.localBits + 16 &&
                    kernels::fragWordFits(plan.keyBits, plan.networkBits);
   // N > 1 pipelines (also on the host path, where they run in place: same
   // logic, covered by the CPU tests).
   plan.splitHistogram = config.splitHistogram && numberOfNodes > 1;
-  plan.pipelineOuter = config.pipelineOuter && numberOfNodes > 1 && !plan.materialize && plan.twoLevel;
+  plan.pipelineOuter = config.pipelineOuter && numberOfNodes > 1 && !plan.carriesRids() && plan.twoLevel;
   // One-sided windows: device engines (IPC-mapped peers) or in-process ranks.
   // Puts move raw tuples and complete at a barrier, so neither the wire codec
   // nor per-chunk pipelining of the outer relation applies.
@@ -545,6 +554,19 @@ std::vector<uint64_t> HashJoin::workspaceParts() const {
   // Build/probe work lists (items or spans, 32 B) and materialized pairs.
   parts[0] += (2 * P + recvTotal[1] / std::max<uint32_t>(plan.sChunk, 1) +
                recvTotal[0] / std::max<uint32_t>(plan.rChunk, 1) + 2048) * 48;
+  if (plan.kind != core::JoinKind::Inner) {
+    // Marks (one bit per slot of the outer local pass output, or of the window
+    // without a local pass), the outer unit arrays (list, counts, 64-bit
+    // offsets) and, materializing, one rid per outer tuple of the window.
+    const uint64_t slots = plan.twoLevel ? kernels::localSampledCapacityBound(
+                                               recvTotal[1], P, std::max<uint32_t>(1, plan.localSampleStride), 64)
+                                         : recvTotal[1];
+    const uint64_t units = P + recvTotal[1] / std::max<uint32_t>(std::min(plan.sChunk, kernels::MARK_UNIT), 1) + 2;
+    parts[0] += kernels::markWords(slots) * 8 + units * (sizeof(kernels::MarkUnit) + 4 + 8) +
+                kernels::scanWorkspaceBytes(units);
+    if (plan.materialize) parts.push_back((recvTotal[1] + 1) * 8);
+    return parts;
+  }
   if (plan.materialize && !config.outputHost)
     parts.push_back((config.outputCapacity ? config.outputCapacity : recvTotal[1] + 1024) * 16);
   return parts;
@@ -576,7 +598,7 @@ void HashJoin::planBitmap() {
                             ((double)innerRelation->getGlobalSize() * wR + (double)outerRelation->getGlobalSize() * wS) /
                             8.0 / std::max<uint32_t>(N, 1);
   }
-  if (!config.bitmapJoin || plan.materialize || plan.wide || plan.keyOnly || plan.keyBits >= 64) return;
+  if (!config.bitmapJoin || plan.carriesRids() || plan.wide || plan.keyOnly || plan.keyBits >= 64) return;
   // Repeated inner keys would only make the bitmap plan fall back after a
   // whole failed join; replicateBitmap = On still forces it (tests of that
   // fallback path).
@@ -704,6 +726,7 @@ bool HashJoin::lowKeyBitsSkewed() {
 }
 
 bool HashJoin::outputValid() const { return output && ctx->workspace().epoch() == outputEpoch; }
+bool HashJoin::outputRidsValid() const { return outputRids && ctx->workspace().epoch() == outputEpoch; }
 
 void HashJoin::join() {
   run();
@@ -711,6 +734,10 @@ void HashJoin::join() {
 }
 
 void HashJoin::setRowSink(const kernels::RowSink &s) {
+  JOIN_ASSERT(plan.kind == core::JoinKind::Inner, "HashJoin",
+              "JoinConfig.kind = %s cannot be combined with a RowSink (join_materialized): a semi- or anti-join has "
+              "outer rids, not (inner, outer) pairs to fetch rows for",
+              core::joinKindName(plan.kind));
   const uint64_t off[2] = {s.offA, s.offB}, rows[2] = {s.rowsAN, s.rowsBN};
   for (int r = 0; r < 2; ++r)
     JOIN_ASSERT(ridLo[r] > ridHi[r] || (ridLo[r] >= off[r] && ridHi[r] - off[r] < rows[r]), "HashJoin",
@@ -722,7 +749,8 @@ void HashJoin::setRowSink(const kernels::RowSink &s) {
 }
 
 bool HashJoin::canFuseRows() const {
-  return ctx->onDevice() && ctx->comm()->size() == 1 && plan.materialize && plan.splitLocal && !plan.wide;
+  return ctx->onDevice() && ctx->comm()->size() == 1 && plan.materialize && plan.kind == core::JoinKind::Inner &&
+         plan.splitLocal && !plan.wide;
 }
 
 JoinResult HashJoin::run() {
@@ -825,6 +853,7 @@ JoinResult HashJoin::runImpl() {
   const uint64_t t4 = nowUs();
   ctx->timeline().resolve();  // every stream was synchronised above
   output = local.buildProbes().empty() ? nullptr : local.buildProbes().front()->getOutput();
+  outputRids = local.buildProbes().empty() ? nullptr : local.buildProbes().front()->getOutputRids();
   outputEpoch = ctx->workspace().epoch();
   local.release();
   result.wireBytes = run.inner->wireBytesSent() + run.outer->wireBytesSent();

@@ -34,6 +34,7 @@ struct JoinResult {
   uint64_t globalMatches = 0;
   uint64_t outputPairs = 0;        // materialize: pairs written on this rank
   bool outputOverflow = false;
+  uint64_t outputRids = 0;         // kind != Inner, materialize: outer rids written on this rank
   bool rowsFused = false;          // materialize: whole rows went to the RowSink (no pair array)
   uint32_t reruns = 0;             // build/probe re-launches after an item/output overflow
   double joinMs = 0;               // host wall: histogram start -> local result available
@@ -96,6 +97,11 @@ class HashJoin {
   // it still is.
   const ulonglong2 *getOutput() const { return output; }
   bool outputValid() const;
+  // kind != Inner with materialize: the outer rids of the last run()
+  // (lastResult().outputRids of them, any order), in the engine's workspace
+  // under the same validity rule as getOutput().
+  const uint64_t *getOutputRids() const { return outputRids; }
+  bool outputRidsValid() const;
   // Fused materialization: while a sink is set, a device join at N = 1 over
   // the split layout writes whole output rows (LateMaterialization's layout)
   // from its materialize pass instead of pairs.  canFuseRows() says whether
@@ -165,6 +171,7 @@ class HashJoin {
   core::JoinPlan basePlan;         // two-level plan (what a bitmap plan falls back to)
   bool bitmapExact = false;        // bitmap plan: exact histograms (small inputs, or after an overflow)
   const ulonglong2 *output = nullptr;
+  const uint64_t *outputRids = nullptr;
   // Capacity spill (planPasses / runPasses): pass count, this rank's and the
   // global tuple counts per pass, the pass buffers (one inner and one outer
   // pass at a time) and the plan's global key / rid bounds.

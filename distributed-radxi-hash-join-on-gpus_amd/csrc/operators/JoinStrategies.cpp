@@ -287,7 +287,9 @@ void LocalPhase::run(JoinRun &run, JoinResult &r) {
     r.buildProbeItems += bp->getWorkItems();
   }
   // Materializing joins have exactly one build/probe (never pipelined).
-  r.outputPairs = env.plan.materialize && !bps.empty() ? bps.front()->getOutputCount() : 0;
+  const bool rids = env.plan.kind != core::JoinKind::Inner;  // semi / anti: outer rids, not pairs
+  r.outputPairs = env.plan.materialize && !rids && !bps.empty() ? bps.front()->getOutputCount() : 0;
+  r.outputRids = env.plan.materialize && rids && !bps.empty() ? bps.front()->getOutputCount() : 0;
   r.outputOverflow = !bps.empty() && bps.front()->outputOverflowed();
   r.rowsFused = !bps.empty() && bps.front()->rowsFused();
   Measurements::stopLocalProcessing();

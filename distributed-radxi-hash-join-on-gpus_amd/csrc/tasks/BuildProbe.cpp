@@ -78,11 +78,96 @@ void BuildProbe::configure() {
   // 2^18 inner tuples into its count table and probes its outer chunk, so a
   // hot partition costs (inner / 2^18) passes over its outer side instead of
   // (inner / rChunk).
-  if (ctx && ctx->onDevice() && kernels::bpDirectSplit(args))
+  // (Semi / anti joins build key sets in LDS: rChunk stays the table's size.)
+  if (ctx && ctx->onDevice() && plan.kind == core::JoinKind::Inner && kernels::bpDirectSplit(args))
     args.rChunk = std::max<uint32_t>(args.rChunk, kernels::BP_DIRECT_R_CHUNK);
   if (capacity == 0)
     capacity = (uint32_t)std::min<uint64_t>(
         0xFFFFFFF0ull, 2ull * args.P + outerPartitionSize / args.sChunk + innerPartitionSize / args.rChunk + 1024);
+}
+
+// Semi / anti join: mark, then compact (kernels/semi_join.hip).  The marks are
+// zeroed here, so every re-run (item-list overflow in collect(), the exact
+// redo after a sampled local pass overflowed) starts from clean marks.
+// The rid list is bounded by the outer tuples of this rank's window: it
+// cannot overflow, so there is no output re-run.
+void BuildProbe::executeMarks() {
+  const bool dev = ctx->onDevice();
+  const bool anti = plan.kind == core::JoinKind::Anti;
+  memory::Arena &ws = ctx->workspace();
+  performance::Timeline &tl = ctx->timeline();
+  const double wb = (double)innerPartitionSize, wp = (double)outerPartitionSize;
+  performance::Measurements::add("BPBUILDELEM", wb, "tuples");
+  performance::Measurements::add("BPPROBEELEM", wp, "tuples");
+  args.materialize = false;  // no pairs; plan.materialize asks for the rid list
+  const uint64_t words = kernels::markWords(windows[1]->getPartitionedCapacity());
+  auto *marks = ws.getArray<unsigned long long>(words);
+  ctx->zero(marks, words * 8);
+  outputCapacity = outerPartitionSize;
+  outRids = nullptr;
+  if (plan.materialize) outRids = ws.getArray<uint64_t>(outputCapacity + 1);
+  if (!dev) {
+    tl.begin("BPTASKTIME");
+    tl.beginSplit("BPKERNEL", "BPBUILD", wb, "BPPROBE", wp);
+    host::buildProbeMark(args, reinterpret_cast<uint64_t *>(marks));
+    matches = host::markCompact(args, reinterpret_cast<const uint64_t *>(marks), anti, outRids, outputCapacity);
+    tl.end("BPKERNEL");
+    tl.end("BPTASKTIME");
+    outputCount = plan.materialize ? matches : 0;
+    workItems = args.P;
+    return;
+  }
+  tl.begin("BPTASKTIME", ctx->stream());
+  const uint64_t tAlloc = performance::nowUs();
+  const uint32_t P1 = std::max<uint32_t>(args.P, 1);
+  // Outer units of the compaction: uargs.sChunk positions of one partition each (kernels::MARK_UNIT).
+  kernels::BPArgs uargs = args;
+  uargs.sChunk = std::min<uint32_t>(args.sChunk, kernels::MARK_UNIT);
+  // sum over partitions of ceil(ns / unit) <= P + total / unit: never overflows
+  // (even: the u32 unit counts are then zeroed as whole words by the engine's own kernel)
+  unitCapacity =
+      (uint32_t)std::min<uint64_t>(0xFFFFFFF0ull, ((uint64_t)args.P + outerPartitionSize / uargs.sChunk + 2) & ~1ull);
+  counters = ws.getArray<unsigned long long>(4);
+  ctx->zero(counters, 4 * sizeof(unsigned long long));
+  args.result = uargs.result = counters;
+  args.outCursor = uargs.outCursor = counters + 1;
+  uint32_t *nItems = reinterpret_cast<uint32_t *>(counters + 2);
+  uint32_t *nUnits = reinterpret_cast<uint32_t *>(counters + 3);
+  uint32_t *counts = ws.getArray<uint32_t>(P1);
+  uint32_t *offsets = ws.getArray<uint32_t>(P1);
+  void *scanWs = ws.get(kernels::scanWorkspaceBytes(std::max<uint64_t>(args.P, unitCapacity)));
+  kernels::BPItem *items = ws.getArray<kernels::BPItem>(capacity);
+  auto *units = ws.getArray<kernels::MarkUnit>(unitCapacity);
+  uint32_t *unitCounts = ws.getArray<uint32_t>(unitCapacity);
+  unsigned long long *unitOffsets = plan.materialize ? ws.getArray<unsigned long long>(unitCapacity) : nullptr;
+  performance::Measurements::add("BPMEMALLOC", (double)(performance::nowUs() - tAlloc), "us");
+  performance::Measurements::add("BPMEMSIZE",
+                                 (double)(2ull * P1 * 4 + kernels::scanWorkspaceBytes(args.P) +
+                                          (uint64_t)capacity * sizeof(kernels::BPItem) + words * 8 +
+                                          (uint64_t)unitCapacity * (sizeof(kernels::MarkUnit) + 12) +
+                                          kernels::bpMarkLdsBytes(args)),
+                                 "bytes");
+  hipStream_t s = ctx->stream();
+  kernels::bpPlanCounts(args, counts, s);
+  kernels::scanExclusiveU32(counts, offsets, args.P, nItems, scanWs, s);
+  kernels::bpEmit(args, counts, offsets, items, capacity, s);
+  tl.beginSplit("BPKERNEL", "BPBUILD", wb, "BPPROBE", wp, s);
+  kernels::bpMark(args, items, nItems, capacity, marks, s);
+  // Outer units (counts / offsets are free again: bpEmit has consumed them in stream order).
+  kernels::markPlanUnits(uargs, counts, s);
+  kernels::scanExclusiveU32(counts, offsets, args.P, nUnits, scanWs, s);
+  kernels::markEmitUnits(uargs, counts, offsets, units, unitCapacity, s);
+  ctx->zero(unitCounts, (uint64_t)unitCapacity * sizeof(uint32_t));
+  kernels::markCount(uargs, units, nUnits, unitCapacity, marks, anti, unitCounts, s);  // -> counters[0]
+  if (plan.materialize) {
+    kernels::scanExclusiveU32to64(unitCounts, unitOffsets, unitCapacity, args.outCursor, scanWs, s);
+    kernels::markPlace(uargs, units, nUnits, unitCapacity, marks, anti, unitOffsets,
+                       reinterpret_cast<unsigned long long *>(outRids), outputCapacity, s);
+  }
+  hipEvent_t done = tl.mark(s);
+  tl.endAt("BPKERNEL", done);
+  tl.endAt("BPTASKTIME", done);
+  readBackCounters();
 }
 
 void BuildProbe::execute() {
@@ -93,6 +178,10 @@ void BuildProbe::execute() {
     return;
   }
   configure();
+  if (plan.kind != core::JoinKind::Inner) {
+    executeMarks();
+    return;
+  }
   const bool dev = ctx->onDevice();
   memory::Arena &ws = ctx->workspace();
   fused = plan.materialize && sink && dev && args.split;
@@ -258,6 +347,20 @@ bool BuildProbe::collect() {
   std::memcpy(h, countersBack, sizeof(h));
   matches = h[0];
   outputCount = h[1];
+  if (plan.kind != core::JoinKind::Inner) {  // [2] item count, [3] unit count (u32 each); the rid list cannot overflow
+    uint32_t nItems, nUnits;
+    std::memcpy(&nItems, &h[2], sizeof(nItems));
+    std::memcpy(&nUnits, &h[3], sizeof(nUnits));
+    workItems = nItems;
+    JOIN_ASSERT(nUnits <= unitCapacity, "BuildProbe", "%u outer units, bound %u", nUnits, unitCapacity);
+    JOIN_ASSERT(!plan.materialize || outputCount == matches, "BuildProbe",
+                "semi/anti join placed %lu rids but counted %lu", (unsigned long)outputCount, (unsigned long)matches);
+    if (nItems > capacity) {
+      capacity = nItems;
+      return true;
+    }
+    return false;
+  }
   uint32_t items, heavy;
   std::memcpy(&items, &h[2], sizeof(items));
   std::memcpy(&heavy, reinterpret_cast<const char *>(&h[2]) + sizeof(items), sizeof(heavy));

@@ -4,6 +4,9 @@
 // read back).  Device flow, all stream-ordered:
 //   plan counts -> wave64 scan (item count stays on the device) -> emit items
 //   -> persistent LDS build/probe kernel -> one 64-bit atomic per workgroup.
+// Semi / anti joins (JoinPlan::kind): the same item list -> bpMark (hit masks
+// into a bit array over the outer positions) -> markCount over outer units
+// -> (materialize) scan -> markPlace writes the outer rids.
 // The host reads the counters once, after the join's single final sync.
 #pragma once
 
@@ -44,6 +47,8 @@ class BuildProbe : public Task {
   uint64_t getOutputCount() const { return outputCount; }
   uint32_t getWorkItems() const { return workItems; }
   const ulonglong2 *getOutput() const { return outPairs; }
+  // kind != Inner, materialize: getOutputCount() outer rids (null otherwise).
+  const uint64_t *getOutputRids() const { return outRids; }
   bool outputOverflowed() const { return overflowOut; }
   // Fused row output (device, split layout): the materialize pass writes whole
   // rows to the sink.  A sink overflow is reported, not re-run (the caller
@@ -65,6 +70,7 @@ class BuildProbe : public Task {
 
  private:
   void configure();
+  void executeMarks();
   core::ExecContext *ctx = nullptr;
   core::JoinPlan plan;
   data::Window *windows[2] = {nullptr, nullptr};
@@ -73,9 +79,12 @@ class BuildProbe : public Task {
   uint64_t outputCapacity = 0;
   // [0] matches [1] out cursor [2] item count (u32) [3] materialize: count-pass
   // matches / key spans: quotient-table side-list overflow flag
+  // semi / anti: [0] qualifying outer tuples [1] rids placed [2] item count (u32) [3] outer unit count (u32)
   unsigned long long *counters = nullptr;
   unsigned long long *countersBack = nullptr;  // pinned copy, enqueued at the end of execute()
   ulonglong2 *outPairs = nullptr;
+  uint64_t *outRids = nullptr;               // semi / anti: outer rid list (workspace)
+  uint32_t unitCapacity = 0;                 // semi / anti: upper bound of the outer units
   std::vector<uint64_t> refBounds;  // reference ctor: partition begin arrays
   uint64_t matches = 0, outputCount = 0;
   uint32_t workItems = 0;

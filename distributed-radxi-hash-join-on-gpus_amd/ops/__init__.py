@@ -6,6 +6,7 @@ host twins (CPU tensors).  Tuples are int64 tensors of shape [n, 2] holding
     v2, begin2 = local_partition(values, begin, 32, 9)   # local pass
     n = build_probe_count(rv, sv, rbeg, sbeg, 41, 32)    # LDS build/probe
     join_count(R, S)                                      # whole engine
+    semi_join(R, S), anti_join(R, S)                      # outer rids with / without an inner partner
 """
 from __future__ import annotations
 
@@ -58,6 +59,15 @@ def build_probe_count(R, S, part_r, part_s, frag_shift: int, key_shift: int) -> 
     return build_probe(R, S, part_r, part_s, frag_shift, key_shift)["matches"]
 
 
+def build_probe_marks(R, S, part_r, part_s, frag_shift: int, key_shift: int, wide=False, r_chunk=4096,
+                      s_chunk=65536) -> dict:
+    """Semi-join marks over matching partitions: ``marks`` (bool [len(S)], by
+    outer position: the tuple's key occurs on the inner side of its partition)
+    and ``semi_count``; also ``anti_count`` and the compacted ``semi_rids`` /
+    ``anti_rids``."""
+    return _C().ops.build_probe_marks(R, S, part_r, part_s, frag_shift, key_shift, wide, r_chunk, s_chunk)
+
+
 def npj_count(R: torch.Tensor, S: torch.Tensor) -> int:
     """No-partitioning join baseline (one global hash table)."""
     return _C().ops.npj_count(R.contiguous(), S.contiguous())
@@ -91,3 +101,33 @@ def join(inner: torch.Tensor, outer: torch.Tensor, config=None) -> torch.Tensor:
     j = _engine(inner, outer, cfg)
     j.run()
     return j.output()
+
+
+def _kind_join(inner, outer, kind: str, materialize: bool, config=None):
+    C = _C()
+    cfg = config or C.JoinConfig()
+    cfg.kind = getattr(C.JoinKind, kind)
+    cfg.materialize = materialize
+    j = _engine(inner, outer, cfg)
+    res = j.run()
+    return j.output_rids() if materialize else res["global_matches"]
+
+
+def semi_join(inner: torch.Tensor, outer: torch.Tensor, config=None) -> torch.Tensor:
+    """Rids (int64 [m], any order) of the outer tuples whose key occurs in ``inner``: each once."""
+    return _kind_join(inner, outer, "SEMI", True, config)
+
+
+def anti_join(inner: torch.Tensor, outer: torch.Tensor, config=None) -> torch.Tensor:
+    """Rids (int64 [m], any order) of the outer tuples whose key does not occur in ``inner``."""
+    return _kind_join(inner, outer, "ANTI", True, config)
+
+
+def semi_join_count(inner: torch.Tensor, outer: torch.Tensor, config=None) -> int:
+    """Number of outer tuples with at least one inner partner (not the inner-join count)."""
+    return _kind_join(inner, outer, "SEMI", False, config)
+
+
+def anti_join_count(inner: torch.Tensor, outer: torch.Tensor, config=None) -> int:
+    """Number of outer tuples with no inner partner."""
+    return _kind_join(inner, outer, "ANTI", False, config)

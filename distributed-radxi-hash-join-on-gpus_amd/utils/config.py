@@ -27,6 +27,7 @@ def config_to_dict(cfg) -> dict:
     d["wire_codec"] = str(cfg.wire_codec).split(".")[-1]
     d["replicate_bitmap"] = str(cfg.replicate_bitmap).split(".")[-1]
     d["exchange"] = str(cfg.exchange).split(".")[-1]
+    d["kind"] = str(cfg.kind).split(".")[-1]
     return d
 
 
@@ -36,7 +37,7 @@ def config_from_dict(d: dict | None = None, env_prefix: str = "HPCJOIN_"):
     cfg = C.JoinConfig()
     merged = dict(d or {})
     for f in _FIELDS + ["assignment", "format", "key_hashing", "network_histogram", "local_histogram", "wire_codec",
-                        "replicate_bitmap", "exchange", "verify_exchange"]:
+                        "replicate_bitmap", "exchange", "verify_exchange", "kind"]:
         v = os.environ.get(env_prefix + f.upper())
         if v is not None:
             merged[f] = v
@@ -55,6 +56,8 @@ def config_from_dict(d: dict | None = None, env_prefix: str = "HPCJOIN_"):
             cfg.wire_codec = getattr(C.WireCodecMode, str(v).upper())
         elif k in ("replicate_bitmap", "verify_exchange"):
             setattr(cfg, k, getattr(C.PlanChoice, str(v).upper()))
+        elif k == "kind":
+            cfg.kind = getattr(C.JoinKind, str(v).upper())
         elif k == "exchange":
             cfg.exchange = getattr(C.ExchangeMode, str(v).upper())
         elif k in _FLOATS:
