@@ -31,6 +31,7 @@ if native_available():
     AssignmentPolicy = _C.AssignmentPolicy
     TupleFormat = _C.TupleFormat
     JoinKind = _C.JoinKind
+    NULL_RID = _C.NULL_RID  # -1 as int64: the padding rid of outer-join rows
     LocalCommunicator = _C.LocalCommunicator
     RcclCommunicator = _C.RcclCommunicator
     ProcessGroupCommunicator = _C.ProcessGroupCommunicator

@@ -6,10 +6,17 @@
 //               [--rank R --world W --id-file PATH]   (one process per GPU; rank 0
 //                                                      writes the ncclUniqueId to PATH)
 //               [--chunks C] [--net-bits B] [--local-bits B] [--materialize] [--wide]
-//               [--round-robin] [--perf-dir DIR] [--kind inner|semi|anti]
+//               [--round-robin] [--perf-dir DIR] [--kind inner|semi|anti|left|right|full]
+//               [--inner-domain D] [--outer-domain D] [--outer-key-offset K]
 // --kind semi|anti: `matches` is the number of outer tuples with / without an
-// inner partner; `correct` is checked against a host oracle computed here
-// when that is cheap (one rank, at most 64M tuples in all), else omitted.
+// inner partner; --kind left|right|full: the number of result rows (the inner
+// join's pairs plus the unmatched tuples of the preserved sides).  `correct`
+// is checked against a host oracle computed here when that is cheap (one
+// rank, at most 64M tuples in all), else omitted.
+// --inner-domain D: inner keys UNIFORM over D keys (repeated and missing
+// keys); --outer-domain / --outer-key-offset: the outer keys' domain and its
+// first key (outer keys without a partner).  With any of them the oracle of
+// every kind is the host one.
 // Default workload per rank: 20M x 20M unique keys, as in main.cpp:70-71.
 #include <hip/hip_runtime.h>
 #include <unistd.h>
@@ -23,6 +30,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
@@ -44,6 +52,7 @@ int main(int argc, char **argv) {
   double theta = 0.75;
   int iters = 5, warmup = 1;
   bool host = false;
+  uint64_t innerDomain = 0, outerDomain = 0, outerKeyOffset = 0;
   core::JoinConfig cfg;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -67,13 +76,19 @@ int main(int argc, char **argv) {
     else if (a == "--round-robin") cfg.assignment = core::AssignmentPolicy::RoundRobin;
     else if (a == "--two-level-only") cfg.bitmapJoin = false;  // no single-level bitmap join (N == 1)
     else if (a == "--perf-dir") perfDir = next();
+    else if (a == "--inner-domain") innerDomain = std::stoull(next());
+    else if (a == "--outer-domain") outerDomain = std::stoull(next());
+    else if (a == "--outer-key-offset") outerKeyOffset = std::stoull(next());
     else if (a == "--kind") {
       const std::string k = next();
       if (k == "inner") cfg.kind = core::JoinKind::Inner;
       else if (k == "semi") cfg.kind = core::JoinKind::Semi;
       else if (k == "anti") cfg.kind = core::JoinKind::Anti;
+      else if (k == "left") cfg.kind = core::JoinKind::LeftOuter;
+      else if (k == "right") cfg.kind = core::JoinKind::RightOuter;
+      else if (k == "full") cfg.kind = core::JoinKind::FullOuter;
       else {
-        std::fprintf(stderr, "unknown --kind %s (inner|semi|anti)\n", k.c_str());
+        std::fprintf(stderr, "unknown --kind %s (inner|semi|anti|left|right|full)\n", k.c_str());
         return 2;
       }
     }
@@ -133,6 +148,19 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "unknown --dist %s\n", dist.c_str());
     return 2;
   }
+  if (innerDomain) {
+    is.distribution = kernels::KeyDistribution::Uniform;
+    is.domain = innerDomain;
+  }
+  if (outerDomain) {
+    if (dist == "unique") {
+      std::fprintf(stderr, "--outer-domain needs --dist modulo|uniform|zipf\n");
+      return 2;
+    }
+    os.domain = outerDomain;
+  }
+  os.keyOffset = outerKeyOffset;
+  const bool customKeys = innerDomain || outerDomain || outerKeyOffset;
   const uint64_t li = data::Relation::localSizeFor(inner, rank, world);
   const uint64_t lo = data::Relation::localSizeFor(outer, rank, world);
   performance::Measurements::writeMetaData("LISZ", li);
@@ -141,20 +169,37 @@ int main(int argc, char **argv) {
   R.generate(is, data::Relation::localOffsetFor(inner, rank, world));
   S.generate(os, data::Relation::localOffsetFor(outer, rank, world));
   uint64_t expected = data::Relation::expectedMatches(is, inner, os, outer);
-  if (cfg.kind != core::JoinKind::Inner) {
+  if (cfg.kind != core::JoinKind::Inner || customKeys) {
     // Host oracle from the same generator specs: the outer tuples whose key is
-    // (semi) / is not (anti) among the inner keys.
+    // (semi) / is not (anti) among the inner keys; outer kinds: the inner
+    // join's matches plus the unmatched tuples of the preserved sides.
     expected = UINT64_MAX;
     if (world == 1 && inner + outer <= (64ull << 20)) {
       data::Relation Rh(inner, inner, Location::Host, 0), Sh(outer, outer, Location::Host, 0);
       Rh.generate(is, 0);
       Sh.generate(os, 0);
-      std::unordered_set<uint64_t> keys;
-      keys.reserve(2 * inner);
-      for (uint64_t i = 0; i < inner; ++i) keys.insert(Rh.getData()[i].key);
-      uint64_t semi = 0;
-      for (uint64_t i = 0; i < outer; ++i) semi += keys.count(Sh.getData()[i].key);
-      expected = cfg.kind == core::JoinKind::Semi ? semi : outer - semi;
+      std::unordered_map<uint64_t, uint64_t> copies;  // inner key -> copies
+      copies.reserve(2 * inner);
+      for (uint64_t i = 0; i < inner; ++i) ++copies[Rh.getData()[i].key];
+      std::unordered_set<uint64_t> probed;  // inner keys some outer tuple has
+      uint64_t semi = 0, pairs = 0, unmatchedInner = 0;
+      for (uint64_t i = 0; i < outer; ++i) {
+        auto it = copies.find(Sh.getData()[i].key);
+        if (it == copies.end()) continue;
+        ++semi;
+        pairs += it->second;
+        probed.insert(it->first);
+      }
+      for (const auto &kc : copies)
+        if (!probed.count(kc.first)) unmatchedInner += kc.second;
+      switch (cfg.kind) {
+        case core::JoinKind::Inner: expected = pairs; break;
+        case core::JoinKind::Semi: expected = semi; break;
+        case core::JoinKind::Anti: expected = outer - semi; break;
+        default:
+          expected = pairs + (core::preservesInner(cfg.kind) ? unmatchedInner : 0) +
+                     (core::preservesOuter(cfg.kind) ? outer - semi : 0);
+      }
     }
   }
 

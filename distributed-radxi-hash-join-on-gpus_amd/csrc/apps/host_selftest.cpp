@@ -11,9 +11,12 @@
 #include <cstdio>
 #include <cstring>
 #include <memory>
+#include <set>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <unordered_set>
+#include <utility>
 #include <vector>
 
 #include "../comm/InProcessCommunicator.h"
@@ -34,7 +37,8 @@ struct Case {
   bool wide, materialize, tpch;
   core::KeyHashing hashing;
   bool wire = false;  // bit-packed exchange (host twin of kernels/wire.hip)
-  core::JoinKind kind = core::JoinKind::Inner;  // semi / anti: outer rids, checked against a set oracle
+  // semi / anti: outer rids, outer kinds: NULL-padded rows, each checked against a set oracle
+  core::JoinKind kind = core::JoinKind::Inner;
 };
 
 bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
@@ -42,7 +46,8 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
   std::vector<std::string> errors(ranks);
   std::vector<uint64_t> matches(ranks, 0), pairs(ranks, 0);
   std::vector<std::vector<uint64_t>> rids(ranks);
-  const bool inner = c.kind == core::JoinKind::Inner;
+  std::vector<std::vector<std::pair<uint64_t, uint64_t>>> rows(ranks);
+  const bool inner = c.kind == core::JoinKind::Inner, outerKind = core::isOuterKind(c.kind);
   data::GenSpec is, os;
   is.seed = 11;
   is.tpchSparse = c.tpch;
@@ -75,7 +80,14 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
       operators::JoinResult res = j.run();
       matches[r] = res.globalMatches;
       pairs[r] = res.outputPairs;
-      if (!inner && c.materialize) rids[r].assign(j.getOutputRids(), j.getOutputRids() + res.outputRids);
+      if (outerKind) {
+        if (res.localMatches != res.matchedPairs + res.unmatchedInner + res.unmatchedOuter ||
+            res.outputPairs != (c.materialize ? res.localMatches : 0) || res.outputRids != 0)
+          throw std::runtime_error("outer join: the result fields do not add up");
+        for (uint64_t i = 0; i < res.outputPairs; ++i) rows[r].emplace_back(j.getOutput()[i].x, j.getOutput()[i].y);
+      } else if (!inner && c.materialize) {
+        rids[r].assign(j.getOutputRids(), j.getOutputRids() + res.outputRids);
+      }
       if (inner && c.materialize) {  // fetch 32-byte payload rows of both sides from their owners
         const uint64_t oR = data::Relation::localOffsetFor(G, r, ranks), oS = data::Relation::localOffsetFor(GS, r, ranks);
         std::vector<uint64_t> rowsR(R.getLocalSize() * kernels::ROW_WORDS), rowsS(S.getLocalSize() * kernels::ROW_WORDS);
@@ -103,7 +115,29 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
   for (auto &t : ts) t.join();
   uint64_t expected = data::Relation::expectedMatches(is, G, os, GS);
   std::unordered_set<uint64_t> expectedRids;
-  if (!inner) {  // the outer tuples whose key is (semi) / is not (anti) among the inner keys
+  std::set<std::pair<uint64_t, uint64_t>> expectedRows;
+  if (outerKind) {  // the inner join's pairs and one NULL-padded row per unmatched tuple of a preserved side
+    data::Relation R(G, G, Location::Host, 0), S(GS, GS, Location::Host, 0);
+    R.generate(is, 0);
+    S.generate(os, 0);
+    std::unordered_map<uint64_t, std::vector<uint64_t>> byKey;
+    std::unordered_set<uint64_t> probed;
+    for (uint64_t i = 0; i < G; ++i) byKey[R.getData()[i].key].push_back(R.getData()[i].rid);
+    for (uint64_t i = 0; i < GS; ++i) {
+      auto it = byKey.find(S.getData()[i].key);
+      if (it == byKey.end()) {
+        if (core::preservesOuter(c.kind)) expectedRows.emplace(kernels::NULL_RID, S.getData()[i].rid);
+        continue;
+      }
+      probed.insert(it->first);
+      for (uint64_t rid : it->second) expectedRows.emplace(rid, S.getData()[i].rid);
+    }
+    if (core::preservesInner(c.kind))
+      for (const auto &kv : byKey)
+        if (!probed.count(kv.first))
+          for (uint64_t rid : kv.second) expectedRows.emplace(rid, kernels::NULL_RID);
+    expected = expectedRows.size();
+  } else if (!inner) {  // the outer tuples whose key is (semi) / is not (anti) among the inner keys
     data::Relation R(G, G, Location::Host, 0), S(GS, GS, Location::Host, 0);
     R.generate(is, 0);
     S.generate(os, 0);
@@ -124,7 +158,16 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
       ok = false;
     }
   }
-  if (ok && c.materialize && !inner) {  // the ranks' rid lists together: the oracle set, no rid twice
+  if (ok && c.materialize && outerKind) {  // the ranks' rows together: the oracle set, no row twice
+    std::set<std::pair<uint64_t, uint64_t>> seen;
+    for (const auto &v : rows)
+      for (const auto &x : v)
+        if (!expectedRows.count(x) || !seen.insert(x).second) ok = false;
+    if (seen.size() != expected) ok = false;
+    if (!ok) std::printf("[%s] rows differ from the oracle (%lu distinct, expected %lu)\n", c.name,
+                         (unsigned long)seen.size(), (unsigned long)expected);
+  }
+  if (ok && c.materialize && !inner && !outerKind) {  // the ranks' rid lists together: the oracle set, no rid twice
     std::unordered_set<uint64_t> seen;
     for (const auto &v : rids)
       for (uint64_t x : v)
@@ -196,6 +239,12 @@ int main(int argc, char **argv) {
        core::JoinKind::Semi},
       {"anti_wide_materialize", kernels::KeyDistribution::Uniform, true, true, false, core::KeyHashing::Auto, false,
        core::JoinKind::Anti},
+      {"left_zipf_materialize", kernels::KeyDistribution::Zipf, false, true, false, core::KeyHashing::Auto, true,
+       core::JoinKind::LeftOuter},
+      {"right_wide_materialize", kernels::KeyDistribution::Uniform, true, true, false, core::KeyHashing::Auto, false,
+       core::JoinKind::RightOuter},
+      {"full_uniform_materialize", kernels::KeyDistribution::Uniform, false, true, false, core::KeyHashing::Auto, false,
+       core::JoinKind::FullOuter},
   };
   bool ok = true;
   for (const Case &c : cases) ok = runCase(c, ranks, G) && ok;

@@ -328,6 +328,151 @@ py::dict opBuildProbeMarks(const at::Tensor &R, const at::Tensor &S, const at::T
   return d;
 }
 
+// ---- outer join over partition-major inputs: count + marks, place, pad -----
+// pairs: int64 [m, 2], the inner join's pairs followed by (rid, NULL_RID) rows
+// of the unmatched inner tuples (keep_inner) and (NULL_RID, rid) rows of the
+// unmatched outer ones (keep_outer); inner_marks / outer_marks: bool per
+// position of R / S (all false for a side that is not kept)
+// (kernels/outer_join.hip and the host twins).
+py::dict opBuildProbeOuter(const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR, const at::Tensor &partS,
+                           int64_t fragShift, int64_t keyShift, bool wide, int64_t rChunk, int64_t sChunk,
+                           bool keepInner, bool keepOuter) {
+  TORCH_CHECK(R.device() == S.device(), "R and S must live on the same device");
+  TORCH_CHECK(rChunk >= 1 && sChunk >= 1, "r_chunk and s_chunk must be positive");
+  TORCH_CHECK(keepInner || keepOuter, "build_probe_outer: keep_inner or keep_outer (or both)");
+  setDevice(R);
+  kernels::BPArgs a;
+  a.R = R.data_ptr();
+  a.S = S.data_ptr();
+  at::Tensor pr = partR.to(R.device()).contiguous(), ps = partS.to(R.device()).contiguous();
+  TORCH_CHECK(pr.size(0) == ps.size(0) && pr.size(0) >= 1, "part_r and part_s must have the same P + 1 entries");
+  a.partR = ptr<uint64_t>(pr);
+  a.partS = ptr<uint64_t>(ps);
+  a.P = (uint32_t)pr.size(0) - 1;
+  a.rChunk = (uint32_t)rChunk;
+  a.sChunk = (uint32_t)sChunk;
+  a.fragShift = (uint32_t)fragShift;
+  a.keyShift = (uint32_t)keyShift;
+  a.wide = wide;
+  const int64_t n[2] = {R.size(0), S.size(0)};
+  const bool keep[2] = {keepInner, keepOuter};
+  at::Tensor marks[2];
+  for (int r = 0; r < 2; ++r) marks[r] = at::zeros({(int64_t)kernels::markWords((uint64_t)n[r])}, like(R));
+  unsigned long long *mp[2] = {keepInner ? ptr<unsigned long long>(marks[0]) : nullptr,
+                               keepOuter ? ptr<unsigned long long>(marks[1]) : nullptr};
+  uint64_t matched = 0, unmatched[2] = {0, 0};
+  at::Tensor pairs;
+  if (R.is_cuda()) {
+    at::Tensor ctr = at::zeros({8}, like(R));
+    auto *c = reinterpret_cast<unsigned long long *>(ctr.data_ptr());
+    a.result = c;
+    a.outCursor = c + 1;
+    uint32_t *nItems = reinterpret_cast<uint32_t *>(c + 2), *nUnits = reinterpret_cast<uint32_t *>(c + 6);
+    const int64_t P1 = std::max<int64_t>(a.P, 1);
+    at::Tensor counts = at::empty({P1}, like(R, at::kInt)), offsets = at::empty({P1}, like(R, at::kInt));
+    kernels::BPArgs ua[2] = {kernels::outerSwapSides(a, std::min<uint32_t>(a.sChunk, kernels::MARK_UNIT)), a};
+    ua[1].sChunk = std::min<uint32_t>(a.sChunk, kernels::MARK_UNIT);
+    uint32_t unitCap[2];
+    for (int r = 0; r < 2; ++r) unitCap[r] = a.P + (uint32_t)(n[r] / ua[r].sChunk) + 1;
+    uint32_t capacity = 2 * a.P + (uint32_t)(n[1] / a.sChunk + n[0] / a.rChunk) + 1024;
+    at::Tensor items, itemCounts, scanWs;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      items = at::empty({(int64_t)capacity * 2}, like(R));
+      itemCounts = at::zeros({(int64_t)capacity}, like(R, at::kInt));
+      scanWs = at::empty({(int64_t)kernels::scanWorkspaceBytes(std::max<uint64_t>(
+                              std::max<uint64_t>(a.P, capacity), std::max(unitCap[0], unitCap[1]))) / 4 + 1},
+                         like(R, at::kInt));
+      ctr.zero_();
+      marks[0].zero_();
+      marks[1].zero_();
+      kernels::bpPlanCounts(a, ptr<uint32_t>(counts), nullptr);
+      kernels::scanExclusiveU32(ptr<uint32_t>(counts), ptr<uint32_t>(offsets), a.P, nItems, scanWs.data_ptr(), nullptr);
+      kernels::bpEmit(a, ptr<uint32_t>(counts), ptr<uint32_t>(offsets), ptr<kernels::BPItem>(items), capacity, nullptr);
+      kernels::BPArgs ca = a;
+      ca.itemCounts = ptr<uint32_t>(itemCounts);
+      kernels::bpOuterCount(ca, ptr<kernels::BPItem>(items), nItems, capacity, mp[0], mp[1], nullptr);
+      HIP_CHECK(hipDeviceSynchronize());
+      const uint32_t need = (uint32_t)(ctr.cpu()[2].item<int64_t>() & 0xFFFFFFFF);
+      if (need <= capacity) break;
+      TORCH_CHECK(attempt == 0, "build_probe_outer: the work-item list overflowed twice");
+      capacity = need;
+    }
+    at::Tensor units[2], unitCounts[2], unitOffsets[2];
+    for (int r = 0; r < 2; ++r) {
+      if (!keep[r]) continue;
+      units[r] = at::empty({(int64_t)unitCap[r]}, like(R));
+      unitCounts[r] = at::zeros({(int64_t)unitCap[r]}, like(R, at::kInt));
+      unitOffsets[r] = at::empty({(int64_t)unitCap[r]}, like(R));
+      ua[r].result = c + 4 + r;
+      kernels::markPlanUnits(ua[r], ptr<uint32_t>(counts), nullptr);
+      kernels::scanExclusiveU32(ptr<uint32_t>(counts), ptr<uint32_t>(offsets), a.P, nUnits + r, scanWs.data_ptr(),
+                                nullptr);
+      kernels::markEmitUnits(ua[r], ptr<uint32_t>(counts), ptr<uint32_t>(offsets), ptr<kernels::MarkUnit>(units[r]),
+                             unitCap[r], nullptr);
+      kernels::markCount(ua[r], ptr<kernels::MarkUnit>(units[r]), nUnits + r, unitCap[r], mp[r], true,
+                         ptr<uint32_t>(unitCounts[r]), nullptr);
+      kernels::scanExclusiveU32to64(ptr<uint32_t>(unitCounts[r]), ptr<unsigned long long>(unitOffsets[r]), unitCap[r],
+                                    nullptr, scanWs.data_ptr(), nullptr);
+    }
+    at::Tensor itemOffsets = at::empty({(int64_t)capacity}, like(R));
+    kernels::scanExclusiveU32to64(ptr<uint32_t>(itemCounts), ptr<unsigned long long>(itemOffsets), capacity, a.outCursor,
+                                  scanWs.data_ptr(), nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    at::Tensor h = ctr.cpu();
+    matched = (uint64_t)h[0].item<int64_t>();
+    TORCH_CHECK((uint64_t)h[1].item<int64_t>() == matched, "build_probe_outer: the item counts do not add up to the pairs");
+    unmatched[0] = (uint64_t)h[4].item<int64_t>();
+    unmatched[1] = (uint64_t)h[5].item<int64_t>();
+    const uint64_t rows = matched + unmatched[0] + unmatched[1];
+    pairs = at::empty({(int64_t)rows, 2}, like(R));
+    a.materialize = true;
+    a.outPairs = reinterpret_cast<ulonglong2 *>(pairs.data_ptr());
+    a.outCapacity = rows;
+    a.itemOffsets = ptr<unsigned long long>(itemOffsets);
+    a.result = c + 3;
+    kernels::buildProbe(a, ptr<kernels::BPItem>(items), nItems, capacity, nullptr);
+    for (int r = 0; r < 2; ++r)
+      if (keep[r])
+        kernels::markPlacePairs(ua[r], ptr<kernels::MarkUnit>(units[r]), nUnits + r, unitCap[r], mp[r],
+                                ptr<unsigned long long>(unitOffsets[r]), c + 1, r ? c + 4 : nullptr, r == 0, a.outPairs,
+                                rows, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    TORCH_CHECK((uint64_t)ctr.cpu()[3].item<int64_t>() == matched, "build_probe_outer: count and place passes disagree");
+  } else {
+    uint64_t cursor = 0, cap = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {  // first a counting walk, then the exactly sized one
+      marks[0].zero_();
+      marks[1].zero_();
+      pairs = at::empty({(int64_t)cap, 2}, like(R));
+      a.materialize = true;
+      a.outPairs = reinterpret_cast<ulonglong2 *>(pairs.data_ptr());
+      a.outCapacity = cap;
+      cursor = 0;
+      a.outCursor = reinterpret_cast<unsigned long long *>(&cursor);
+      matched = host::buildProbeOuter(a, reinterpret_cast<uint64_t *>(mp[0]), reinterpret_cast<uint64_t *>(mp[1]));
+      for (int r = 0; r < 2; ++r)
+        unmatched[r] = keep[r] ? host::markCompactPairs(a, reinterpret_cast<const uint64_t *>(mp[r]), r == 0,
+                                                        a.outPairs, &cursor, cap)
+                               : 0;
+      cap = cursor;
+    }
+  }
+  py::dict d;
+  const char *names[2] = {"inner_marks", "outer_marks"};
+  for (int r = 0; r < 2; ++r) {
+    at::Tensor pos = at::arange(n[r], like(R));
+    d[names[r]] = at::bitwise_and(at::bitwise_right_shift(marks[r].index_select(0, at::bitwise_right_shift(pos, 6)),
+                                                          at::bitwise_and(pos, 63)),
+                                  1)
+                      .to(at::kBool);
+  }
+  d["pairs"] = pairs;
+  d["matched_pairs"] = matched;
+  d["unmatched_inner"] = unmatched[0];
+  d["unmatched_outer"] = unmatched[1];
+  return d;
+}
+
 at::Tensor opGenerate(int64_t n, int64_t globalOffset, int64_t globalSize, const data::GenSpec &spec,
                       const std::string &device) {
   at::Tensor out = at::empty({n, 2}, at::TensorOptions().dtype(at::kLong).device(device));
@@ -653,6 +798,9 @@ py::dict resultToDict(const operators::JoinResult &r) {
   d["global_matches"] = r.globalMatches;
   d["output_pairs"] = r.outputPairs;
   d["output_rids"] = r.outputRids;
+  d["matched_pairs"] = r.matchedPairs;
+  d["unmatched_inner"] = r.unmatchedInner;
+  d["unmatched_outer"] = r.unmatchedOuter;
   d["output_overflow"] = r.outputOverflow;
   d["rows_fused"] = r.rowsFused;
   d["split_partitions"] = r.splitPartitions;
@@ -728,6 +876,7 @@ static void checkPayloadCover(const operators::HashJoin &j, const at::Tensor &a,
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "MI355X-native distributed radix hash join engine (native core)";
   m.attr("ARCH") = "gfx950";
+  m.attr("NULL_RID") = (int64_t)kernels::NULL_RID;  // -1 as int64: the padding rid of outer-join rows
 
   m.def("device_count", []() {
     int n = 0;
@@ -771,7 +920,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   py::enum_<core::JoinKind>(m, "JoinKind")
       .value("INNER", core::JoinKind::Inner)
       .value("SEMI", core::JoinKind::Semi)
-      .value("ANTI", core::JoinKind::Anti);
+      .value("ANTI", core::JoinKind::Anti)
+      .value("LEFT_OUTER", core::JoinKind::LeftOuter)
+      .value("RIGHT_OUTER", core::JoinKind::RightOuter)
+      .value("FULL_OUTER", core::JoinKind::FullOuter);
   py::class_<core::JoinConfig>(m, "JoinConfig")
       .def(py::init<>())
       .def_readwrite("kind", &core::JoinConfig::kind)
@@ -1189,7 +1341,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
             TORCH_CHECK(j.getConfig().materialize, "join was not run with materialize=True");
             TORCH_CHECK(j.getConfig().kind == core::JoinKind::Inner,
                         "materialize_payloads needs kind=INNER: a kind=SEMI / ANTI join has outer rids "
-                        "(output_rids()), not pairs");
+                        "(output_rids()), not pairs, and an outer kind has NULL rids without a row");
             TORCH_CHECK(!j.lastResult().rowsFused, "the last run wrote rows directly (join_materialized)");
             TORCH_CHECK(innerRows.dim() == 2 && innerRows.size(1) == (int64_t)kernels::ROW_WORDS &&
                             outerRows.dim() == 2 && outerRows.size(1) == (int64_t)kernels::ROW_WORDS,
@@ -1225,8 +1377,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
             // (no pair array); otherwise run() + LateMaterialization.
             TORCH_CHECK(j.getConfig().materialize, "join_materialized needs materialize=True");
             TORCH_CHECK(j.getConfig().kind == core::JoinKind::Inner,
-                        "join_materialized cannot be combined with kind=SEMI / ANTI: such a join has outer rids "
-                        "(output_rids()), not (inner, outer) pairs to fetch rows for");
+                        "join_materialized cannot be combined with kind=SEMI / ANTI / LEFT_OUTER / RIGHT_OUTER / "
+                        "FULL_OUTER: such a join has outer rids (output_rids()) or NULL rids without a row, not "
+                        "(inner, outer) pairs to fetch rows for");
             TORCH_CHECK(innerRows.dim() == 2 && innerRows.size(1) == (int64_t)kernels::ROW_WORDS &&
                             outerRows.dim() == 2 && outerRows.size(1) == (int64_t)kernels::ROW_WORDS,
                         "payload rows must be [n, 4] int64 (32 bytes)");
@@ -1400,6 +1553,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   ops.def("build_probe_marks", &opBuildProbeMarks, py::arg("R"), py::arg("S"), py::arg("part_r"), py::arg("part_s"),
           py::arg("frag_shift"), py::arg("key_shift"), py::arg("wide") = false, py::arg("r_chunk") = 4096,
           py::arg("s_chunk") = 65536);
+  ops.def("build_probe_outer", &opBuildProbeOuter, py::arg("R"), py::arg("S"), py::arg("part_r"), py::arg("part_s"),
+          py::arg("frag_shift"), py::arg("key_shift"), py::arg("wide") = false, py::arg("r_chunk") = 4096,
+          py::arg("s_chunk") = 65536, py::arg("keep_inner") = true, py::arg("keep_outer") = true);
   ops.def("generate", &opGenerate, py::arg("n"), py::arg("global_offset"), py::arg("global_size"), py::arg("spec"),
           py::arg("device") = "cpu");
   ops.def("scan_u32", &opScan);

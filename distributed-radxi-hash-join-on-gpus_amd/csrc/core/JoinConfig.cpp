@@ -59,8 +59,9 @@ JoinPlan makePlan(const JoinConfig &cfg, uint32_t numberOfNodes, uint64_t global
   // is 1024: with their 32-byte payload rows (32 KiB) they fit the LDS of the
   // fused row-output kernel, 3 workgroups per CU (kernels/build_probe.hip,
   // bpMatRowsKernel).  SF100: 35.6 ms fused vs 42.0 ms join + separate pass.
-  // (Semi / anti joins keep keys only in LDS: sized as counting joins.)
-  const bool pairs = p.materialize && p.kind == JoinKind::Inner;
+  // (Semi / anti joins keep keys only in LDS: sized as counting joins.  A
+  // materializing outer join runs the inner join's place pass: sized like it.)
+  const bool pairs = p.materialize && !isRidKind(p.kind);
   const bool matNarrow = pairs && !p.wide && !cfg.rChunk;
   const uint32_t matTarget = numberOfNodes == 1 ? 1024 : 2048;
   // >= 8 network partitions per node so LPT has room to balance.

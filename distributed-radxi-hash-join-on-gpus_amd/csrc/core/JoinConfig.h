@@ -66,20 +66,43 @@ enum class ExchangeMode : int {
                  // (IPC-mapped peer allocations; plain pointers for in-process ranks), then a barrier
 };
 
-// What a join answers about R |x| S.  Semi: the outer tuples with at least one
-// inner partner; Anti: those with none.  Each qualifying outer tuple counts,
-// and is emitted, exactly once however many inner copies its key has
-// (kernels/semi_join.hip: mark, then compact).
-enum class JoinKind : int { Inner = 0, Semi = 1, Anti = 2 };
+// What a join answers about R |x| S.  R is the inner relation (build side,
+// first argument), S the outer relation (probe side, second argument); no kind
+// swaps them.
+//   Semi / Anti: the outer tuples with at least one inner partner / with none.
+//     Each qualifying outer tuple counts, and is emitted, exactly once however
+//     many inner copies its key has (kernels/semi_join.hip: mark, then compact).
+//   LeftOuter / RightOuter / FullOuter: the inner join's (rid_inner, rid_outer)
+//     pairs, plus one row (rid, NULL_RID) per R tuple without a partner (left,
+//     full) and one row (NULL_RID, rid) per S tuple without a partner (right,
+//     full); NULL_RID = ~0 (kernels::NULL_RID).  A preserved tuple with
+//     partners appears only in its pairs.  Row order is unspecified.
+//     local_matches / global_matches count the result rows (pairs plus
+//     unmatched preserved tuples); JoinResult::matchedPairs / unmatchedInner /
+//     unmatchedOuter split them (kernels/outer_join.hip).
+enum class JoinKind : int { Inner = 0, Semi = 1, Anti = 2, LeftOuter = 3, RightOuter = 4, FullOuter = 5 };
 inline const char *joinKindName(JoinKind k) {
-  return k == JoinKind::Semi ? "semi" : k == JoinKind::Anti ? "anti" : "inner";
+  switch (k) {
+    case JoinKind::Semi: return "semi";
+    case JoinKind::Anti: return "anti";
+    case JoinKind::LeftOuter: return "left";
+    case JoinKind::RightOuter: return "right";
+    case JoinKind::FullOuter: return "full";
+    default: return "inner";
+  }
 }
+inline bool preservesInner(JoinKind k) { return k == JoinKind::LeftOuter || k == JoinKind::FullOuter; }
+inline bool preservesOuter(JoinKind k) { return k == JoinKind::RightOuter || k == JoinKind::FullOuter; }
+inline bool isOuterKind(JoinKind k) { return preservesInner(k) || preservesOuter(k); }
+inline bool isRidKind(JoinKind k) { return k == JoinKind::Semi || k == JoinKind::Anti; }  // answers with outer rids
 
 struct JoinConfig {
   // Semi / Anti: local_matches / global_matches count the qualifying outer
   // tuples, and with materialize the output is a list of outer rids
-  // (HashJoin::getOutputRids) instead of pairs.  Not combined with outputHost,
-  // a RowSink, or a materializing capacity spill.
+  // (HashJoin::getOutputRids) instead of pairs.  Outer kinds: with materialize
+  // the output is the NULL-padded pair list (HashJoin::getOutput); refused when
+  // a rid equals NULL_RID.  No kind but Inner is combined with outputHost, a
+  // RowSink, or a materializing capacity spill.
   JoinKind kind = JoinKind::Inner;
   uint32_t networkBits = 0;   // radix bits of the network pass (0 = auto)
   uint32_t localBits = 0;     // radix bits of the local pass (0 = auto; ignored if !twoLevel)
@@ -123,7 +146,8 @@ struct JoinConfig {
   // is joined by several ranks (larger side divided, smaller replicated;
   // histograms/AssignmentMap).  Forced off for kind != Inner: a hot partition
   // joined by several ranks may divide its inner side and replicate its outer
-  // side, which would mark one outer tuple on several ranks.
+  // side, which would mark one outer tuple on several ranks (outer kinds: a
+  // replicated tuple unmatched on one rank may be matched on another).
   bool skewSplit = true;
   bool directCount = true;      // count-only build/probe: direct-addressed LDS counts when fragments are <= 13 bits
   bool splitHistogram = true;   // N > 1 on device: outer exact histogram overlaps the inner exchange

@@ -283,6 +283,71 @@ uint64_t markCompact(const kernels::BPArgs &a, const uint64_t *marks, bool anti,
   return n;
 }
 
+uint64_t buildProbeOuter(const kernels::BPArgs &a, uint64_t *marksR, uint64_t *marksS) {
+  uint64_t pairs = 0;
+  const uint64_t ridMask = a.keyShift >= 64 ? ~0ull : ((1ull << a.keyShift) - 1);
+  std::vector<uint64_t> bucket, next;
+  auto key = [&](const void *base, uint64_t i) -> uint64_t {
+    if (a.wide) return static_cast<const data::Tuple *>(base)[i].key;
+    return a.keyShift >= 64 ? 0ull : static_cast<const uint64_t *>(base)[i] >> a.keyShift;
+  };
+  auto rid = [&](const void *base, uint64_t i) -> uint64_t {
+    return a.wide ? static_cast<const data::Tuple *>(base)[i].rid : (static_cast<const uint64_t *>(base)[i] & ridMask);
+  };
+  for (uint32_t p = 0; p < a.P; ++p) {
+    const uint64_t rb = a.partR[p], re = a.partREnd ? a.partREnd[p] : a.partR[p + 1], sb = a.partS[p],
+                   se = a.partSEnd ? a.partSEnd[p] : a.partS[p + 1];
+    const uint64_t nr = re - rb;
+    if (nr == 0 || se == sb) continue;  // one-sided partitions: nothing is marked
+    const uint64_t N = nextPow2(nr);
+    bucket.assign(N, 0);
+    next.assign(nr, 0);
+    for (uint64_t t = 0; t < nr; ++t) {
+      const uint64_t idx = kernels::mix64(key(a.R, rb + t)) & (N - 1);
+      next[t] = bucket[idx];
+      bucket[idx] = t + 1;
+    }
+    for (uint64_t s = sb; s < se; ++s) {
+      const uint64_t k = key(a.S, s);
+      bool any = false;
+      for (uint64_t hit = bucket[kernels::mix64(k) & (N - 1)]; hit > 0; hit = next[hit - 1]) {
+        const uint64_t r = rb + hit - 1;
+        if (key(a.R, r) != k) continue;
+        any = true;
+        ++pairs;
+        if (marksR) marksR[r >> 6] |= 1ull << (r & 63);
+        if (a.materialize) {
+          const unsigned long long pos = (*a.outCursor)++;
+          if (pos < a.outCapacity) a.outPairs[pos] = make_ulonglong2(rid(a.R, r), rid(a.S, s));
+        }
+      }
+      if (any && marksS) marksS[s >> 6] |= 1ull << (s & 63);
+    }
+  }
+  return pairs;
+}
+
+uint64_t markCompactPairs(const kernels::BPArgs &a, const uint64_t *marks, bool innerSide, ulonglong2 *out,
+                          uint64_t *cursor, uint64_t outCapacity) {
+  const uint64_t ridMask = a.keyShift >= 64 ? ~0ull : ((1ull << a.keyShift) - 1);
+  const void *base = innerSide ? a.R : a.S;
+  const uint64_t *pb = innerSide ? a.partR : a.partS, *pe = innerSide ? a.partREnd : a.partSEnd;
+  uint64_t n = 0;
+  for (uint32_t p = 0; p < a.P; ++p) {
+    const uint64_t b = pb[p], e = pe ? pe[p] : pb[p + 1];
+    for (uint64_t i = b; i < e; ++i) {
+      if ((marks[i >> 6] >> (i & 63)) & 1) continue;
+      const uint64_t rid =
+          a.wide ? static_cast<const data::Tuple *>(base)[i].rid : (static_cast<const uint64_t *>(base)[i] & ridMask);
+      const uint64_t at = (*cursor)++;
+      if (out && at < outCapacity)
+        out[at] = innerSide ? make_ulonglong2(rid, kernels::NULL_RID) : make_ulonglong2(kernels::NULL_RID, rid);
+      ++n;
+    }
+  }
+  return n;
+}
+
 uint64_t npjJoin(const data::Tuple *R, uint64_t nR, const data::Tuple *S, uint64_t nS) {
   std::unordered_map<uint64_t, uint64_t> counts;
   counts.reserve(nR * 2);

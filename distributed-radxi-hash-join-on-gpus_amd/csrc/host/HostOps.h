@@ -47,6 +47,18 @@ uint64_t buildProbe(const kernels::BPArgs &a);
 // out != null, appends their rids (at most outCapacity are written).
 void buildProbeMark(const kernels::BPArgs &a, uint64_t *marks);
 uint64_t markCompact(const kernels::BPArgs &a, const uint64_t *marks, bool anti, uint64_t *out, uint64_t outCapacity);
+// Outer joins (twins of kernels/outer_join.hip).  buildProbeOuter walks whole
+// partitions with the bucket-chained table: returns the pairs, written (when
+// a.materialize) through a.outPairs / a.outCursor as buildProbe does, and sets
+// bit r of marksR / bit s of marksS (each optional, zeroed by the caller) for
+// every inner / outer position with a partner.  markCompactPairs appends one
+// row {rid, NULL_RID} (innerSide: the partitions of a.R) or {NULL_RID, rid}
+// (those of a.S) per unmarked position from out[*cursor] (out may be null;
+// rows at or beyond outCapacity are counted, not stored) and returns their
+// number.
+uint64_t buildProbeOuter(const kernels::BPArgs &a, uint64_t *marksR, uint64_t *marksS);
+uint64_t markCompactPairs(const kernels::BPArgs &a, const uint64_t *marks, bool innerSide, ulonglong2 *out,
+                          uint64_t *cursor, uint64_t outCapacity);
 
 // Wire codec (kernels.h, WireCodec) over host segment lists.
 void wirePack(const uint64_t *raw, uint64_t *wire, const kernels::WireSeg *segs, uint32_t nSegs,

@@ -531,6 +531,32 @@ void markPlace(const BPArgs &a, const MarkUnit *units, const uint32_t *nUnits, u
                const unsigned long long *marks, bool anti, const unsigned long long *unitOffsets,
                unsigned long long *out, uint64_t outCapacity, hipStream_t s);
 
+// Left / right / full outer joins (outer_join.hip; core::JoinKind): the inner
+// join's pairs plus one row (rid, NULL_RID) per unmatched inner tuple and one
+// row (NULL_RID, rid) per unmatched outer tuple of a preserved side.
+constexpr unsigned long long NULL_RID = ~0ull;
+size_t bpOuterLdsBytes(const BPArgs &a);
+// Replaces the count pre-pass of the two-pass pair materialization: over the
+// BPItem list, a.itemCounts[w] = pairs of item w (with multiplicity), their sum
+// added to *a.result, and -- each optional, zeroed by the caller, markWords(n)
+// words -- marksR / marksS: one bit per position of the partitioned inner /
+// outer buffer, set when the tuple there has a partner.  Reads every key once.
+// Layouts: CompressedTuples, split columns, wide tuples (not key-only words).
+void bpOuterCount(const BPArgs &a, const BPItem *items, const uint32_t *nItems, uint32_t capacity,
+                  unsigned long long *marksR, unsigned long long *marksS, hipStream_t s);
+// `a` with the inner side in the outer side's place (S, Shi, partS, partSEnd)
+// and units of `unit` positions: markPlanUnits / markEmitUnits / markCount /
+// markPlacePairs then walk the inner relation's partitions.
+BPArgs outerSwapSides(const BPArgs &a, uint32_t unit);
+// The pair-writing twin of markPlace over the units of a.S: one row per
+// unmarked tuple, {rid, NULL_RID} (innerSide) or {NULL_RID, rid}, at
+// out[*base0 + *base1 + unitOffsets[u] ...] in position order (base1 may be
+// null; rows at or beyond outCapacity are not stored).
+void markPlacePairs(const BPArgs &a, const MarkUnit *units, const uint32_t *nUnits, uint32_t capacity,
+                    const unsigned long long *marks, const unsigned long long *unitOffsets,
+                    const unsigned long long *base0, const unsigned long long *base1, bool innerSide, ulonglong2 *out,
+                    uint64_t outCapacity, hipStream_t s);
+
 // Single-level counting join of unique inner keys (bitmap_join.hip): one
 // workgroup per network partition sets a 2^bits LDS bitmap from the inner
 // fragments and tests the outer ones.
@@ -832,6 +858,7 @@ void preloadScatterAblation();
 void preloadBuildProbe();
 void preloadKeyTables();
 void preloadSemiJoin();
+void preloadOuterJoin();
 void preloadBitmapJoin();
 void preloadScan();
 void preloadWire();
@@ -845,6 +872,7 @@ inline void preloadCodeObjects() {
   preloadBuildProbe();
   preloadKeyTables();
   preloadSemiJoin();
+  preloadOuterJoin();
   preloadBitmapJoin();
   preloadScan();
   preloadWire();

@@ -116,8 +116,8 @@ void HashJoin::planPasses() {
   passes = K;
   if (K == 1) return;
   JOIN_ASSERT(!plan.materialize || plan.kind == core::JoinKind::Inner, "HashJoin",
-              "capacity spill (%u passes) of a materializing JoinConfig.kind = %s join is not supported: the rid list "
-              "lives in the workspace; count-only semi- and anti-joins do spill",
+              "capacity spill (%u passes) of a materializing JoinConfig.kind = %s join is not supported: its rid or row "
+              "list lives in the workspace; count-only semi-, anti- and outer joins do spill",
               K, core::joinKindName(plan.kind));
   JOIN_ASSERT(!plan.materialize || config.outputHost, "HashJoin",
               "capacity spill (%u passes) of a materializing join needs JoinConfig.outputHost: the pairs of every "
@@ -253,6 +253,9 @@ JoinResult HashJoin::runPasses() {
       total.outputPairs += r.outputPairs;
     }
     total.localMatches += r.localMatches;
+    total.matchedPairs += r.matchedPairs;  // outer kinds: a pass holds every copy of a key from both sides
+    total.unmatchedInner += r.unmatchedInner;
+    total.unmatchedOuter += r.unmatchedOuter;
     total.globalMatches += r.globalMatches;
     total.innerReceived += r.innerReceived;
     total.outerReceived += r.outerReceived;
@@ -292,7 +295,7 @@ void HashJoin::makeJoinPlan() {
               "relations must live where the engine runs (%s) or in pinned host memory", locationName(ctx->location()));
   JOIN_ASSERT(config.kind == core::JoinKind::Inner || !config.outputHost, "HashJoin",
               "JoinConfig.kind = %s cannot be combined with JoinConfig.outputHost (output_host): a semi- or anti-join "
-              "writes outer rids to the workspace, not pairs to a host buffer",
+              "writes outer rids, and an outer join its NULL-padded rows, to the workspace, not pairs to a host buffer",
               core::joinKindName(config.kind));
   // Max key / rid over both relations and all ranks (the plan must be identical
   // everywhere), plus each rank's rid range per relation and exchange chunk
@@ -368,6 +371,9 @@ void HashJoin::makeJoinPlan() {
                         mx[1]);
   planMaxKey = mx[0];
   planMaxRid = mx[1];
+  JOIN_ASSERT(!core::isOuterKind(config.kind) || planMaxRid != kernels::NULL_RID, "HashJoin",
+              "JoinConfig.kind = %s: a rid equals NULL_RID (0xFFFFFFFFFFFFFFFF), which pads the unmatched rows",
+              core::joinKindName(config.kind));
   // Repeated inner keys are known before the first join (generator metadata
   // or the sample above): no bitmap plan to attempt and throw away, and
   // key-only words go on counted tables from the first join instead of
@@ -554,6 +560,28 @@ std::vector<uint64_t> HashJoin::workspaceParts() const {
   // Build/probe work lists (items or spans, 32 B) and materialized pairs.
   parts[0] += (2 * P + recvTotal[1] / std::max<uint32_t>(plan.sChunk, 1) +
                recvTotal[0] / std::max<uint32_t>(plan.rChunk, 1) + 2048) * 48;
+  if (core::isOuterKind(plan.kind)) {
+    // Marks and unit arrays (list, counts, 64-bit offsets) per preserved side,
+    // per-item pair counts and offsets, and the row buffer at its default
+    // capacity (tasks/BuildProbe, executeOuter).
+    const uint64_t items = 2 * P + recvTotal[1] / std::max<uint32_t>(plan.sChunk, 1) +
+                           recvTotal[0] / std::max<uint32_t>(plan.rChunk, 1) + 1024;
+    uint64_t small = items * (4 + 8) + kernels::scanWorkspaceBytes(items), rows = recvTotal[1] + 1024;
+    for (int r = 0; r < 2; ++r) {
+      if (!(r == 0 ? core::preservesInner(plan.kind) : core::preservesOuter(plan.kind))) continue;
+      const uint64_t slots = plan.twoLevel ? kernels::localSampledCapacityBound(
+                                                 recvTotal[r], P, std::max<uint32_t>(1, plan.localSampleStride), 64)
+                                           : recvTotal[r];
+      const uint32_t unit = r == 0 ? kernels::MARK_UNIT : std::min(plan.sChunk, kernels::MARK_UNIT);
+      const uint64_t units = P + recvTotal[r] / std::max<uint32_t>(unit, 1) + 2;
+      small += kernels::markWords(slots) * 8 + units * (sizeof(kernels::MarkUnit) + 4 + 8) +
+               kernels::scanWorkspaceBytes(units);
+      if (r == 0) rows += recvTotal[0];
+    }
+    parts[0] += small;
+    if (plan.materialize) parts.push_back((config.outputCapacity ? config.outputCapacity : rows) * 16);
+    return parts;
+  }
   if (plan.kind != core::JoinKind::Inner) {
     // Marks (one bit per slot of the outer local pass output, or of the window
     // without a local pass), the outer unit arrays (list, counts, 64-bit
@@ -736,7 +764,7 @@ void HashJoin::join() {
 void HashJoin::setRowSink(const kernels::RowSink &s) {
   JOIN_ASSERT(plan.kind == core::JoinKind::Inner, "HashJoin",
               "JoinConfig.kind = %s cannot be combined with a RowSink (join_materialized): a semi- or anti-join has "
-              "outer rids, not (inner, outer) pairs to fetch rows for",
+              "outer rids, and an outer join NULL rids without a row, not (inner, outer) pairs to fetch rows for",
               core::joinKindName(plan.kind));
   const uint64_t off[2] = {s.offA, s.offB}, rows[2] = {s.rowsAN, s.rowsBN};
   for (int r = 0; r < 2; ++r)

@@ -34,7 +34,11 @@ struct JoinResult {
   uint64_t globalMatches = 0;
   uint64_t outputPairs = 0;        // materialize: pairs written on this rank
   bool outputOverflow = false;
-  uint64_t outputRids = 0;         // kind != Inner, materialize: outer rids written on this rank
+  uint64_t outputRids = 0;         // kind Semi / Anti, materialize: outer rids written on this rank
+  // Outer kinds, local to the rank: localMatches = matchedPairs + unmatchedInner
+  // + unmatchedOuter (the result rows); an unmatched count is 0 for a side
+  // that is not preserved.  With materialize, outputPairs rows are written.
+  uint64_t matchedPairs = 0, unmatchedInner = 0, unmatchedOuter = 0;
   bool rowsFused = false;          // materialize: whole rows went to the RowSink (no pair array)
   uint32_t reruns = 0;             // build/probe re-launches after an item/output overflow
   double joinMs = 0;               // host wall: histogram start -> local result available
@@ -91,7 +95,8 @@ class HashJoin {
   const core::JoinPlan &getPlan() const { return plan; }
   const core::JoinConfig &getConfig() const { return config; }
   core::ExecContext *context() const { return ctx; }
-  // Materialized (rid_inner, rid_outer) pairs of the last run(), in the engine's workspace: valid
+  // Materialized (rid_inner, rid_outer) pairs of the last run() (outer kinds:
+  // followed by the NULL-padded rows of the unmatched preserved tuples), in the engine's workspace: valid
   // until the workspace is rewound or freed (the next join on the context,
   // a new HashJoin planned on it, trim_workspace).  outputValid() says whether
   // it still is.

@@ -287,9 +287,14 @@ void LocalPhase::run(JoinRun &run, JoinResult &r) {
     r.buildProbeItems += bp->getWorkItems();
   }
   // Materializing joins have exactly one build/probe (never pipelined).
-  const bool rids = env.plan.kind != core::JoinKind::Inner;  // semi / anti: outer rids, not pairs
+  const bool rids = core::isRidKind(env.plan.kind);  // semi / anti: outer rids; inner and outer kinds: pairs
   r.outputPairs = env.plan.materialize && !rids && !bps.empty() ? bps.front()->getOutputCount() : 0;
   r.outputRids = env.plan.materialize && rids && !bps.empty() ? bps.front()->getOutputCount() : 0;
+  if (core::isOuterKind(env.plan.kind) && !bps.empty()) {  // (never pipelined: one build/probe)
+    r.matchedPairs = bps.front()->getMatchedPairs();
+    r.unmatchedInner = bps.front()->getUnmatchedInner();
+    r.unmatchedOuter = bps.front()->getUnmatchedOuter();
+  }
   r.outputOverflow = !bps.empty() && bps.front()->outputOverflowed();
   r.rowsFused = !bps.empty() && bps.front()->rowsFused();
   Measurements::stopLocalProcessing();

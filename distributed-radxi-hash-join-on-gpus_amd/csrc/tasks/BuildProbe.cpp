@@ -14,6 +14,9 @@
 namespace hpcjoin {
 namespace tasks {
 
+// Device counter block, read back once per execute() (BuildProbe.h, counters).
+static constexpr uint32_t kCounters = 8;
+
 BuildProbe::BuildProbe(uint64_t innerPartitionSize, data::CompressedTuple *innerPartition,
                        uint64_t outerPartitionSize, data::CompressedTuple *outerPartition)
     : innerPartitionSize(innerPartitionSize), innerPartition(innerPartition), outerPartitionSize(outerPartitionSize),
@@ -79,6 +82,7 @@ void BuildProbe::configure() {
   // hot partition costs (inner / 2^18) passes over its outer side instead of
   // (inner / rChunk).
   // (Semi / anti joins build key sets in LDS: rChunk stays the table's size.)
+  // (Outer joins build key multisets in LDS as well.)
   if (ctx && ctx->onDevice() && plan.kind == core::JoinKind::Inner && kernels::bpDirectSplit(args))
     args.rChunk = std::max<uint32_t>(args.rChunk, kernels::BP_DIRECT_R_CHUNK);
   if (capacity == 0)
@@ -127,8 +131,8 @@ void BuildProbe::executeMarks() {
   // (even: the u32 unit counts are then zeroed as whole words by the engine's own kernel)
   unitCapacity =
       (uint32_t)std::min<uint64_t>(0xFFFFFFF0ull, ((uint64_t)args.P + outerPartitionSize / uargs.sChunk + 2) & ~1ull);
-  counters = ws.getArray<unsigned long long>(4);
-  ctx->zero(counters, 4 * sizeof(unsigned long long));
+  counters = ws.getArray<unsigned long long>(kCounters);
+  ctx->zero(counters, kCounters * sizeof(unsigned long long));
   args.result = uargs.result = counters;
   args.outCursor = uargs.outCursor = counters + 1;
   uint32_t *nItems = reinterpret_cast<uint32_t *>(counters + 2);
@@ -170,6 +174,166 @@ void BuildProbe::executeMarks() {
   readBackCounters();
 }
 
+// Left / right / full outer join (kernels/outer_join.hip): the two-pass pair
+// materialization with bpOuterCount as its count pass (per-item pair counts
+// and the hit marks of the preserved sides from one read of the keys), the
+// unchanged place pass, and per preserved side the unit compaction of the
+// unmarked tuples into NULL-padded rows behind the pairs.  Marks, item counts
+// and unit counts are zeroed here, so every re-run (item-list or output
+// overflow in collect(), the exact redo after a sampled local pass
+// overflowed) starts from clean marks.
+void BuildProbe::executeOuter() {
+  const bool dev = ctx->onDevice();
+  const bool keepR = core::preservesInner(plan.kind), keepS = core::preservesOuter(plan.kind);
+  memory::Arena &ws = ctx->workspace();
+  performance::Timeline &tl = ctx->timeline();
+  const double wb = (double)innerPartitionSize, wp = (double)outerPartitionSize;
+  performance::Measurements::add("BPBUILDELEM", wb, "tuples");
+  performance::Measurements::add("BPPROBEELEM", wp, "tuples");
+  const uint64_t wordsR = keepR ? kernels::markWords(windows[0]->getPartitionedCapacity()) : 0;
+  const uint64_t wordsS = keepS ? kernels::markWords(windows[1]->getPartitionedCapacity()) : 0;
+  auto *marksR = keepR ? ws.getArray<unsigned long long>(wordsR) : nullptr;
+  auto *marksS = keepS ? ws.getArray<unsigned long long>(wordsS) : nullptr;
+  if (keepR) ctx->zero(marksR, wordsR * 8);
+  if (keepS) ctx->zero(marksS, wordsS * 8);
+  outPairs = nullptr;
+  args.materialize = plan.materialize;
+  if (plan.materialize) {
+    // The unmatched rows alone never overflow the default; the pairs can (repeated keys): collect() grows it.
+    if (outputCapacity == 0) outputCapacity = outerPartitionSize + 1024 + (keepR ? innerPartitionSize : 0);
+    outPairs = static_cast<ulonglong2 *>(ws.get(outputCapacity * sizeof(ulonglong2)));
+    args.outPairs = outPairs;
+    args.outCapacity = outputCapacity;
+  }
+  if (!dev) {
+    tl.begin("BPTASKTIME");
+    tl.beginSplit("BPKERNEL", "BPBUILD", wb, "BPPROBE", wp);
+    for (;;) {
+      hostCursor = 0;
+      args.outCursor = reinterpret_cast<unsigned long long *>(&hostCursor);
+      matchedPairs = host::buildProbeOuter(args, reinterpret_cast<uint64_t *>(marksR), reinterpret_cast<uint64_t *>(marksS));
+      if (!plan.materialize) hostCursor = matchedPairs;
+      unmatchedInner = keepR ? host::markCompactPairs(args, reinterpret_cast<const uint64_t *>(marksR), true, outPairs,
+                                                      &hostCursor, outputCapacity)
+                             : 0;
+      unmatchedOuter = keepS ? host::markCompactPairs(args, reinterpret_cast<const uint64_t *>(marksS), false, outPairs,
+                                                      &hostCursor, outputCapacity)
+                             : 0;
+      if (!plan.materialize || hostCursor <= outputCapacity) break;
+      // more pairs than the default capacity (repeated keys): once more, exactly sized, from clean marks
+      outputCapacity = hostCursor;
+      outPairs = static_cast<ulonglong2 *>(ws.get(outputCapacity * sizeof(ulonglong2)));
+      args.outPairs = outPairs;
+      args.outCapacity = outputCapacity;
+      if (keepR) ctx->zero(marksR, wordsR * 8);
+      if (keepS) ctx->zero(marksS, wordsS * 8);
+    }
+    tl.end("BPKERNEL");
+    tl.end("BPTASKTIME");
+    matches = matchedPairs + unmatchedInner + unmatchedOuter;
+    outputCount = plan.materialize ? hostCursor : 0;
+    workItems = args.P;
+    return;
+  }
+  tl.begin("BPTASKTIME", ctx->stream());
+  const uint64_t tAlloc = performance::nowUs();
+  const uint32_t P1 = std::max<uint32_t>(args.P, 1);
+  // Units of the compaction, per preserved side: runs of one partition's
+  // positions (kernels::MARK_UNIT); the inner side through swapped arguments.
+  const kernels::BPArgs rargs0 = kernels::outerSwapSides(args, kernels::MARK_UNIT);
+  kernels::BPArgs sargs0 = args;
+  sargs0.sChunk = std::min<uint32_t>(args.sChunk, kernels::MARK_UNIT);
+  // sum over partitions of ceil(n / unit) <= P + total / unit: never overflows (even: zeroed as whole words)
+  auto unitBound = [&](uint64_t n, uint32_t unit) {
+    return (uint32_t)std::min<uint64_t>(0xFFFFFFF0ull, ((uint64_t)args.P + n / unit + 2) & ~1ull);
+  };
+  unitCapacityR = keepR ? unitBound(innerPartitionSize, rargs0.sChunk) : 0;
+  unitCapacity = keepS ? unitBound(outerPartitionSize, sargs0.sChunk) : 0;
+  const uint32_t itemWords = (capacity + 1) & ~1u;  // u32 item counts, zeroed as whole words
+  counters = ws.getArray<unsigned long long>(kCounters);
+  ctx->zero(counters, kCounters * sizeof(unsigned long long));
+  args.result = counters;         // [0] pairs (count pass)
+  args.outCursor = counters + 1;  // [1] pairs (scan total of the item counts)
+  uint32_t *nItems = reinterpret_cast<uint32_t *>(counters + 2);
+  uint32_t *nUnitsR = reinterpret_cast<uint32_t *>(counters + 6), *nUnitsS = nUnitsR + 1;
+  uint32_t *counts = ws.getArray<uint32_t>(P1);
+  uint32_t *offsets = ws.getArray<uint32_t>(P1);
+  const uint64_t scanN = std::max<uint64_t>(std::max<uint64_t>(args.P, capacity), std::max(unitCapacityR, unitCapacity));
+  void *scanWs = ws.get(kernels::scanWorkspaceBytes(scanN));
+  kernels::BPItem *items = ws.getArray<kernels::BPItem>(capacity);
+  uint32_t *itemCounts = ws.getArray<uint32_t>(itemWords);
+  unsigned long long *itemOffsets = plan.materialize ? ws.getArray<unsigned long long>(capacity) : nullptr;
+  struct Side {
+    kernels::BPArgs a;
+    uint32_t cap = 0, *nUnits = nullptr, *unitCounts = nullptr;
+    kernels::MarkUnit *units = nullptr;
+    unsigned long long *unitOffsets = nullptr, *marks = nullptr;
+  } side[2];
+  side[0].a = rargs0;
+  side[0].cap = unitCapacityR;
+  side[0].nUnits = nUnitsR;
+  side[0].marks = marksR;
+  side[1].a = sargs0;
+  side[1].cap = unitCapacity;
+  side[1].nUnits = nUnitsS;
+  side[1].marks = marksS;
+  uint64_t unitBytes = 0;
+  for (int r = 0; r < 2; ++r) {
+    Side &sd = side[r];
+    if (!sd.cap) continue;
+    sd.units = ws.getArray<kernels::MarkUnit>(sd.cap);
+    sd.unitCounts = ws.getArray<uint32_t>(sd.cap);
+    if (plan.materialize) sd.unitOffsets = ws.getArray<unsigned long long>(sd.cap);
+    sd.a.result = counters + 4 + r;  // [4] unmatched inner, [5] unmatched outer
+    unitBytes += (uint64_t)sd.cap * (sizeof(kernels::MarkUnit) + 12);
+  }
+  performance::Measurements::add("BPMEMALLOC", (double)(performance::nowUs() - tAlloc), "us");
+  performance::Measurements::add("BPMEMSIZE",
+                                 (double)(2ull * P1 * 4 + kernels::scanWorkspaceBytes(scanN) +
+                                          (uint64_t)capacity * (sizeof(kernels::BPItem) + 12) + (wordsR + wordsS) * 8 +
+                                          unitBytes + kernels::bpOuterLdsBytes(args)),
+                                 "bytes");
+  hipStream_t s = ctx->stream();
+  kernels::bpPlanCounts(args, counts, s);
+  kernels::scanExclusiveU32(counts, offsets, args.P, nItems, scanWs, s);
+  kernels::bpEmit(args, counts, offsets, items, capacity, s);
+  ctx->zero(itemCounts, (uint64_t)itemWords * sizeof(uint32_t));
+  for (const Side &sd : side)
+    if (sd.cap) ctx->zero(sd.unitCounts, (uint64_t)sd.cap * sizeof(uint32_t));
+  tl.beginSplit("BPKERNEL", "BPBUILD", wb, "BPPROBE", wp, s);
+  kernels::BPArgs countArgs = args;
+  countArgs.materialize = false;
+  countArgs.itemCounts = itemCounts;
+  kernels::bpOuterCount(countArgs, items, nItems, capacity, marksR, marksS, s);  // -> counters[0], marks
+  // Unit lists (counts / offsets are free again: bpEmit has consumed them in stream order), unmatched counts.
+  for (const Side &sd : side) {
+    if (!sd.cap) continue;
+    kernels::markPlanUnits(sd.a, counts, s);
+    kernels::scanExclusiveU32(counts, offsets, args.P, sd.nUnits, scanWs, s);
+    kernels::markEmitUnits(sd.a, counts, offsets, sd.units, sd.cap, s);
+    kernels::markCount(sd.a, sd.units, sd.nUnits, sd.cap, sd.marks, true, sd.unitCounts, s);  // -> counters[4 + side]
+  }
+  if (plan.materialize) {
+    kernels::scanExclusiveU32to64(itemCounts, itemOffsets, capacity, args.outCursor, scanWs, s);
+    for (const Side &sd : side)
+      if (sd.cap) kernels::scanExclusiveU32to64(sd.unitCounts, sd.unitOffsets, sd.cap, nullptr, scanWs, s);
+    args.itemOffsets = itemOffsets;
+    args.result = counters + 3;  // the count pass already counted
+    kernels::buildProbe(args, items, nItems, capacity, s);  // the inner join's place pass, unchanged
+    // Unmatched rows behind the pairs: inner side from [1], outer side from [1] + [4] ([4] = 0 unless R is preserved).
+    if (keepR)
+      kernels::markPlacePairs(side[0].a, side[0].units, nUnitsR, side[0].cap, marksR, side[0].unitOffsets, counters + 1,
+                              nullptr, true, outPairs, outputCapacity, s);
+    if (keepS)
+      kernels::markPlacePairs(side[1].a, side[1].units, nUnitsS, side[1].cap, marksS, side[1].unitOffsets, counters + 1,
+                              counters + 4, false, outPairs, outputCapacity, s);
+  }
+  hipEvent_t done = tl.mark(s);
+  tl.endAt("BPKERNEL", done);
+  tl.endAt("BPTASKTIME", done);
+  readBackCounters();
+}
+
 void BuildProbe::execute() {
   if (reference) {
     args.result = nullptr;
@@ -178,6 +342,10 @@ void BuildProbe::execute() {
     return;
   }
   configure();
+  if (core::isOuterKind(plan.kind)) {
+    executeOuter();
+    return;
+  }
   if (plan.kind != core::JoinKind::Inner) {
     executeMarks();
     return;
@@ -225,8 +393,8 @@ void BuildProbe::execute() {
   }
   tl.begin("BPTASKTIME", ctx->stream());
   const uint64_t tAlloc = performance::nowUs();
-  counters = ws.getArray<unsigned long long>(4);
-  ctx->zero(counters, 4 * sizeof(unsigned long long));
+  counters = ws.getArray<unsigned long long>(kCounters);
+  ctx->zero(counters, kCounters * sizeof(unsigned long long));
   args.result = counters;
   args.outCursor = counters + 1;
   uint32_t *nItems = reinterpret_cast<uint32_t *>(counters + 2);
@@ -333,8 +501,8 @@ void BuildProbe::execute() {
 // Enqueued behind the build/probe, so the join's final synchronisation also
 // completes the read-back (no separate blocking copy afterwards).
 void BuildProbe::readBackCounters() {
-  countersBack = ctx->staging().getArray<unsigned long long>(4);
-  ctx->readBack(countersBack, counters, 4 * sizeof(unsigned long long));
+  countersBack = ctx->staging().getArray<unsigned long long>(kCounters);
+  ctx->readBack(countersBack, counters, kCounters * sizeof(unsigned long long));
 }
 
 bool BuildProbe::collect() {
@@ -342,11 +510,40 @@ bool BuildProbe::collect() {
     overflowOut = plan.materialize && outputCount > outputCapacity;
     return false;
   }
-  unsigned long long h[4];
+  unsigned long long h[kCounters];
   HIP_CHECK(hipStreamSynchronize(ctx->stream()));  // no-op after the caller's sync
   std::memcpy(h, countersBack, sizeof(h));
   matches = h[0];
   outputCount = h[1];
+  if (core::isOuterKind(plan.kind)) {
+    // [0] pairs [1] pairs by the scan [2] item count (u32) [4] unmatched inner [5] unmatched outer
+    // [6] inner / outer unit counts (u32 each)
+    uint32_t nItems, nUnits[2];
+    std::memcpy(&nItems, &h[2], sizeof(nItems));
+    std::memcpy(nUnits, &h[6], sizeof(nUnits));
+    workItems = nItems;
+    matchedPairs = h[0];
+    unmatchedInner = h[4];
+    unmatchedOuter = h[5];
+    matches = matchedPairs + unmatchedInner + unmatchedOuter;
+    // The true row total, also when stores were clipped at the capacity.
+    outputCount = plan.materialize ? matches : 0;
+    JOIN_ASSERT(nUnits[0] <= unitCapacityR && nUnits[1] <= unitCapacity, "BuildProbe",
+                "%u inner / %u outer units, bounds %u / %u", nUnits[0], nUnits[1], unitCapacityR, unitCapacity);
+    bool again = false;
+    if (nItems > capacity) {
+      capacity = nItems;
+      again = true;
+    } else {
+      JOIN_ASSERT(!plan.materialize || h[1] == h[0], "BuildProbe", "outer join: item counts sum to %lu pairs, counted %lu",
+                  (unsigned long)h[1], (unsigned long)h[0]);
+    }
+    if (plan.materialize && outputCount > outputCapacity) {
+      outputCapacity = outputCount;
+      again = true;
+    }
+    return again;
+  }
   if (plan.kind != core::JoinKind::Inner) {  // [2] item count, [3] unit count (u32 each); the rid list cannot overflow
     uint32_t nItems, nUnits;
     std::memcpy(&nItems, &h[2], sizeof(nItems));

@@ -7,6 +7,10 @@
 // Semi / anti joins (JoinPlan::kind): the same item list -> bpMark (hit masks
 // into a bit array over the outer positions) -> markCount over outer units
 // -> (materialize) scan -> markPlace writes the outer rids.
+// Outer joins: the same item list -> bpOuterCount (per-item pair counts and
+// the hit marks of the preserved sides) -> markCount(anti) over the units of
+// each preserved side -> (materialize) scans -> the inner join's place pass
+// -> markPlacePairs appends the NULL-padded rows (kernels/outer_join.hip).
 // The host reads the counters once, after the join's single final sync.
 #pragma once
 
@@ -46,6 +50,10 @@ class BuildProbe : public Task {
   uint64_t getMatches() const { return matches; }
   uint64_t getOutputCount() const { return outputCount; }
   uint32_t getWorkItems() const { return workItems; }
+  // Outer kinds: getMatches() = pairs + unmatched tuples of the preserved sides.
+  uint64_t getMatchedPairs() const { return matchedPairs; }
+  uint64_t getUnmatchedInner() const { return unmatchedInner; }
+  uint64_t getUnmatchedOuter() const { return unmatchedOuter; }
   const ulonglong2 *getOutput() const { return outPairs; }
   // kind != Inner, materialize: getOutputCount() outer rids (null otherwise).
   const uint64_t *getOutputRids() const { return outRids; }
@@ -71,6 +79,7 @@ class BuildProbe : public Task {
  private:
   void configure();
   void executeMarks();
+  void executeOuter();
   core::ExecContext *ctx = nullptr;
   core::JoinPlan plan;
   data::Window *windows[2] = {nullptr, nullptr};
@@ -80,11 +89,15 @@ class BuildProbe : public Task {
   // [0] matches [1] out cursor [2] item count (u32) [3] materialize: count-pass
   // matches / key spans: quotient-table side-list overflow flag
   // semi / anti: [0] qualifying outer tuples [1] rids placed [2] item count (u32) [3] outer unit count (u32)
+  // outer kinds: [0] pairs [1] pairs by the item-count scan [2] item count (u32) [3] place-pass matches (unused)
+  // [4] unmatched inner [5] unmatched outer [6] inner / outer unit counts (u32 each) [7] spare
   unsigned long long *counters = nullptr;
   unsigned long long *countersBack = nullptr;  // pinned copy, enqueued at the end of execute()
   ulonglong2 *outPairs = nullptr;
   uint64_t *outRids = nullptr;               // semi / anti: outer rid list (workspace)
-  uint32_t unitCapacity = 0;                 // semi / anti: upper bound of the outer units
+  uint32_t unitCapacity = 0;                 // semi / anti / outer kinds: upper bound of the outer units
+  uint32_t unitCapacityR = 0;                // outer kinds preserving R: upper bound of the inner units
+  uint64_t matchedPairs = 0, unmatchedInner = 0, unmatchedOuter = 0;  // outer kinds (matches = their sum)
   std::vector<uint64_t> refBounds;  // reference ctor: partition begin arrays
   uint64_t matches = 0, outputCount = 0;
   uint32_t workItems = 0;

@@ -7,6 +7,7 @@ host twins (CPU tensors).  Tuples are int64 tensors of shape [n, 2] holding
     n = build_probe_count(rv, sv, rbeg, sbeg, 41, 32)    # LDS build/probe
     join_count(R, S)                                      # whole engine
     semi_join(R, S), anti_join(R, S)                      # outer rids with / without an inner partner
+    left_outer_join(R, S), right_outer_join(R, S), full_outer_join(R, S)   # pairs + NULL_RID-padded rows
 """
 from __future__ import annotations
 
@@ -66,6 +67,18 @@ def build_probe_marks(R, S, part_r, part_s, frag_shift: int, key_shift: int, wid
     and ``semi_count``; also ``anti_count`` and the compacted ``semi_rids`` /
     ``anti_rids``."""
     return _C().ops.build_probe_marks(R, S, part_r, part_s, frag_shift, key_shift, wide, r_chunk, s_chunk)
+
+
+def build_probe_outer(R, S, part_r, part_s, frag_shift: int, key_shift: int, wide=False, r_chunk=4096,
+                      s_chunk=65536, keep_inner=True, keep_outer=True) -> dict:
+    """Outer join over matching partitions: ``pairs`` (int64 [m, 2]: the inner
+    join's (inner rid, outer rid) pairs, then ``(rid, NULL_RID)`` per unmatched
+    inner tuple if ``keep_inner`` and ``(NULL_RID, rid)`` per unmatched outer
+    tuple if ``keep_outer``), ``matched_pairs``, ``unmatched_inner``,
+    ``unmatched_outer`` and ``inner_marks`` / ``outer_marks`` (bool per
+    position of R / S: the tuple has a partner; all false for a side not kept)."""
+    return _C().ops.build_probe_outer(R, S, part_r, part_s, frag_shift, key_shift, wide, r_chunk, s_chunk,
+                                      keep_inner, keep_outer)
 
 
 def npj_count(R: torch.Tensor, S: torch.Tensor) -> int:
@@ -131,3 +144,48 @@ def semi_join_count(inner: torch.Tensor, outer: torch.Tensor, config=None) -> in
 def anti_join_count(inner: torch.Tensor, outer: torch.Tensor, config=None) -> int:
     """Number of outer tuples with no inner partner."""
     return _kind_join(inner, outer, "ANTI", False, config)
+
+
+# Padding rid of an outer join's unmatched rows (~0 as uint64, -1 as int64).
+NULL_RID = -1
+
+
+def _outer_join(inner, outer, kind: str, materialize: bool, config=None):
+    C = _C()
+    cfg = config or C.JoinConfig()
+    cfg.kind = getattr(C.JoinKind, kind)
+    cfg.materialize = materialize
+    j = _engine(inner, outer, cfg)
+    res = j.run()
+    return j.output() if materialize else res["global_matches"]
+
+
+def left_outer_join(inner: torch.Tensor, outer: torch.Tensor, config=None) -> torch.Tensor:
+    """int64 [m, 2]: the join's (inner rid, outer rid) pairs plus ``(rid, NULL_RID)`` per inner tuple without a
+    partner; any order."""
+    return _outer_join(inner, outer, "LEFT_OUTER", True, config)
+
+
+def right_outer_join(inner: torch.Tensor, outer: torch.Tensor, config=None) -> torch.Tensor:
+    """int64 [m, 2]: the join's pairs plus ``(NULL_RID, rid)`` per outer tuple without a partner; any order."""
+    return _outer_join(inner, outer, "RIGHT_OUTER", True, config)
+
+
+def full_outer_join(inner: torch.Tensor, outer: torch.Tensor, config=None) -> torch.Tensor:
+    """int64 [m, 2]: the join's pairs plus the NULL_RID-padded rows of both sides' tuples without a partner."""
+    return _outer_join(inner, outer, "FULL_OUTER", True, config)
+
+
+def left_outer_join_count(inner: torch.Tensor, outer: torch.Tensor, config=None) -> int:
+    """Rows of ``left_outer_join``: pairs + inner tuples without a partner."""
+    return _outer_join(inner, outer, "LEFT_OUTER", False, config)
+
+
+def right_outer_join_count(inner: torch.Tensor, outer: torch.Tensor, config=None) -> int:
+    """Rows of ``right_outer_join``: pairs + outer tuples without a partner."""
+    return _outer_join(inner, outer, "RIGHT_OUTER", False, config)
+
+
+def full_outer_join_count(inner: torch.Tensor, outer: torch.Tensor, config=None) -> int:
+    """Rows of ``full_outer_join``."""
+    return _outer_join(inner, outer, "FULL_OUTER", False, config)
