@@ -182,9 +182,23 @@ std::tuple<at::Tensor, at::Tensor> opLocalPartition(const at::Tensor &values, co
 // ---- build/probe over partition-major inputs -----------------------------
 py::dict opBuildProbe(const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR, const at::Tensor &partS,
                       int64_t fragShift, int64_t keyShift, bool wide, bool materialize, int64_t rChunk,
-                      int64_t sChunk, int64_t outCapacity) {
+                      int64_t sChunk, int64_t outCapacity, int64_t fragBits) {
   setDevice(R);
   kernels::BPArgs a;
+  // frag_bits > 0 promises fragments below 2^frag_bits (small values select the
+  // direct-addressed count table, which indexes LDS by the fragment): checked
+  // here.  The host twin has no such table and ignores it.
+  TORCH_CHECK(fragBits >= 0 && fragBits <= 32, "frag_bits must lie in [0, 32]");
+  if (fragBits > 0) {
+    TORCH_CHECK(!wide && fragShift >= 0 && fragShift < 64, "frag_bits applies to compressed tuples");
+    for (const at::Tensor *t : {&R, &S})
+      if (t->numel() > 0) {
+        at::Tensor f = t->bitwise_right_shift(fragShift);
+        TORCH_CHECK(f.min().item<int64_t>() >= 0 && f.max().item<int64_t>() < ((int64_t)1 << fragBits),
+                    "build_probe: a fragment does not fit frag_bits = ", fragBits);
+      }
+    a.fragBits = (uint32_t)fragBits;
+  }
   a.R = R.data_ptr();
   a.S = S.data_ptr();
   at::Tensor pr = partR.to(R.device()).contiguous(), ps = partS.to(R.device()).contiguous();
@@ -497,6 +511,180 @@ at::Tensor opGenerate(int64_t n, int64_t globalOffset, int64_t globalSize, const
     host::generate(ptr<data::Tuple>(out), n, p);
   }
   return out;
+}
+
+// ---- LDS bitmap kernels (kernels/bitmap_join.hip) on caller-laid windows ----
+// One side of a bitmap kernel: the fragment window (int32: u32 fragments with
+// claim slices start / cur / end [CLAIM_GROUPS, F], int32 or int64 cursors;
+// int64: 8-byte words with a segment table seg_start / seg_len [F, groups]).
+// Every slice is checked against the window here, so a wrong test input is an
+// error and not an out-of-bounds read.
+struct BitmapSide {
+  at::Tensor window;
+  c10::optional<at::Tensor> start, cur, end, segStart, segLen;
+};
+
+struct BitmapShape {
+  int64_t partitions, keyShift, bits, threads, flat;
+  c10::optional<at::Tensor> roundMeta;
+};
+
+// Keeps the tensors the returned BitmapSlices points into.
+struct BitmapSideArgs {
+  kernels::BitmapSlices sl;
+  uint32_t elemBytes = 0;
+  std::vector<at::Tensor> keep;
+};
+
+BitmapSideArgs bitmapSide(const BitmapSide &s, const BitmapShape &sh, const char *name) {
+  BitmapSideArgs out;
+  const at::Tensor &w = s.window;
+  TORCH_CHECK(w.is_cuda() && w.dim() == 1 && w.is_contiguous() &&
+                  (w.scalar_type() == at::kInt || w.scalar_type() == at::kLong),
+              name, ": the window must be a contiguous 1-D int32 or int64 HIP tensor");
+  TORCH_CHECK(sh.partitions >= 0 && sh.partitions <= (int64_t)1 << 20, name, ": partitions out of range");
+  TORCH_CHECK(sh.threads == 0 || sh.threads == 256 || sh.threads == 1024, "threads must be 0, 256 or 1024");
+  TORCH_CHECK(sh.flat >= -1 && sh.flat <= 1, "flat must be -1, 0 or 1");
+  out.elemBytes = w.scalar_type() == at::kInt ? 4 : 8;
+  const int64_t n = w.numel(), F = sh.partitions;
+  out.sl.count = (uint64_t)n;
+  out.sl.threads = (uint32_t)sh.threads;
+  out.sl.flat = (int32_t)sh.flat;
+  if (out.elemBytes == 4) {
+    TORCH_CHECK(s.start && s.cur && s.end && !s.segStart && !s.segLen, name, ": u32 fragments need start / cur / end");
+    const at::Tensor &a = *s.start, &c = *s.cur, &e = *s.end;
+    for (const at::Tensor *t : {&a, &c, &e})
+      TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->dim() == 2 && t->size(0) == kernels::CLAIM_GROUPS &&
+                      t->size(1) == F && t->scalar_type() == a.scalar_type() &&
+                      (t->scalar_type() == at::kInt || t->scalar_type() == at::kLong),
+                  name, ": claim slices must be contiguous [", kernels::CLAIM_GROUPS, ", partitions] int32 or int64");
+    kernels::RoundMap rm;
+    if (sh.roundMeta) {
+      const at::Tensor &m = *sh.roundMeta;
+      TORCH_CHECK(m.is_cuda() && m.is_contiguous() && m.scalar_type() == at::kInt && m.numel() == 4,
+                  "round_meta must be a HIP int32 tensor {lp, lv, lns, 0}");
+      at::Tensor h = m.cpu();
+      rm.lp = (uint32_t)h[0].item<int32_t>();
+      rm.lv = (uint32_t)h[1].item<int32_t>();
+      rm.lns = (uint32_t)h[2].item<int32_t>();
+      TORCH_CHECK(!rm.on() || (rm.lp >= 2 && rm.lp <= rm.lv && rm.lv + rm.lns < 48),
+                  "round_meta: pieces hold whole 16-byte vectors (2 <= lp <= lv)");
+      out.sl.roundMeta = ptr<const uint32_t>(m);
+      out.keep.push_back(m);
+    }
+    // Unsigned view of the cursors, as the kernels read them.
+    auto host = [&](const at::Tensor &t) {
+      at::Tensor h = t.cpu().to(at::kLong);
+      return t.scalar_type() == at::kInt ? h.bitwise_and((int64_t)0xFFFFFFFFll) : h;
+    };
+    at::Tensor ha = host(a), hc = host(c), he = host(e);
+    const int64_t *pa = ha.data_ptr<int64_t>(), *pc = hc.data_ptr<int64_t>(), *pe = he.data_ptr<int64_t>();
+    for (int64_t i = 0; i < ha.numel(); ++i) {
+      TORCH_CHECK(pa[i] >= 0 && pa[i] <= pe[i] && pa[i] <= pc[i] && pa[i] % 16 == 0, name, ": slice ", i,
+                  " must start on a 16-element boundary, not after its end or its cursor");
+      if (pa[i] == pe[i]) continue;
+      if (rm.on())
+        TORCH_CHECK((pa[i] >> rm.lv) == ((pe[i] - 1) >> rm.lv) && ((uint64_t)pa[i] >> rm.lv) < (1ull << rm.lns),
+                    name, ": slice ", i, " leaves its round-interleaved slot range");
+      TORCH_CHECK(rm((uint64_t)pe[i] - 1) < (uint64_t)n, name, ": slice ", i, " ends outside the window");
+    }
+    out.sl.kind = kernels::BitmapSlices::Claim;
+    out.sl.narrow = a.scalar_type() == at::kInt;
+    out.sl.start = a.data_ptr();
+    out.sl.cur = c.data_ptr();
+    out.sl.end = e.data_ptr();
+    out.keep.insert(out.keep.end(), {a, c, e});
+  } else {
+    TORCH_CHECK(s.segStart && s.segLen && !s.start && !s.cur && !s.end, name,
+                ": 8-byte words need a segment table seg_start / seg_len");
+    TORCH_CHECK(!sh.roundMeta, "round_meta applies to u32 fragment windows only");
+    const at::Tensor &a = *s.segStart, &l = *s.segLen;
+    for (const at::Tensor *t : {&a, &l})
+      TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->dim() == 2 && t->size(0) == F && t->size(1) >= 1 &&
+                      t->size(1) == a.size(1) && t->scalar_type() == at::kLong,
+                  name, ": the segment table must be contiguous [partitions, groups] int64");
+    at::Tensor ha = a.cpu(), hl = l.cpu();
+    const int64_t *pa = ha.data_ptr<int64_t>(), *pl = hl.data_ptr<int64_t>();
+    for (int64_t i = 0; i < ha.numel(); ++i)
+      TORCH_CHECK(pa[i] >= 0 && pl[i] >= 0 && pa[i] <= n && pl[i] <= n - pa[i], name, ": segment ", i,
+                  " lies outside the window");
+    out.sl.kind = kernels::BitmapSlices::Table;
+    out.sl.segStart = ptr<const uint64_t>(a);
+    out.sl.segLen = ptr<const uint64_t>(l);
+    out.sl.groups = (uint32_t)a.size(1);
+    out.keep.insert(out.keep.end(), {a, l});
+  }
+  return out;
+}
+
+int64_t bitmapTotalWords(int64_t bits) {
+  TORCH_CHECK(bits >= 0 && bits <= (int64_t)(kernels::BITMAP_MAX_BITS + kernels::BITMAP_MAX_SPLIT),
+              "bitmap kernels: bits out of range");
+  const uint32_t split = bits > (int64_t)kernels::BITMAP_MAX_BITS ? (uint32_t)bits - kernels::BITMAP_MAX_BITS : 0;
+  return (int64_t)kernels::bitmapWords((uint32_t)bits - split) << split;
+}
+
+py::dict bitmapCountersDict(const at::Tensor &ctr) {
+  at::Tensor h = ctr.cpu();
+  py::dict d;
+  d["matches"] = (uint64_t)h[0].item<int64_t>();
+  d["popcount"] = (uint64_t)h[1].item<int64_t>();
+  d["dup"] = (uint64_t)h[2].item<int64_t>();
+  d["overflow"] = (uint64_t)h[3].item<int64_t>();
+  return d;
+}
+
+uint32_t bitmapRange(int64_t partitions, int64_t first, int64_t count) {
+  TORCH_CHECK(first >= 0 && first <= partitions && (count < 0 || count <= partitions - first),
+              "bitmap kernels: partitions [first, first + count) out of range");
+  return count < 0 ? (uint32_t)(partitions - first) : (uint32_t)count;
+}
+
+py::dict opBitmapBuild(const BitmapSide &r, const BitmapShape &sh, int64_t first, int64_t count) {
+  setDevice(r.window);
+  BitmapSideArgs a = bitmapSide(r, sh, "bitmap_build");
+  const int64_t words = bitmapTotalWords(sh.bits);
+  const uint32_t cnt = bitmapRange(sh.partitions, first, count);
+  at::Tensor bitmaps = at::zeros({sh.partitions, words}, like(r.window, at::kInt));
+  at::Tensor ctr = at::zeros({4}, like(r.window));
+  kernels::bitmapBuild(a.elemBytes, r.window.data_ptr(), a.sl, (uint32_t)sh.partitions, (uint32_t)sh.keyShift,
+                       (uint32_t)sh.bits, ptr<uint32_t>(bitmaps), ptr<kernels::BitmapCounters>(ctr), nullptr,
+                       (uint32_t)first, cnt);
+  HIP_CHECK(hipDeviceSynchronize());
+  py::dict d = bitmapCountersDict(ctr);
+  d["bitmaps"] = bitmaps;
+  return d;
+}
+
+py::dict opBitmapProbe(const BitmapSide &s, const at::Tensor &bitmaps, const BitmapShape &sh, int64_t first,
+                       int64_t count) {
+  setDevice(s.window);
+  BitmapSideArgs a = bitmapSide(s, sh, "bitmap_probe");
+  const int64_t words = bitmapTotalWords(sh.bits);
+  const uint32_t cnt = bitmapRange(sh.partitions, first, count);
+  TORCH_CHECK(bitmaps.is_cuda() && bitmaps.is_contiguous() && bitmaps.scalar_type() == at::kInt &&
+                  bitmaps.numel() == sh.partitions * words,
+              "bitmap_probe: bitmaps must be a contiguous HIP int32 tensor [partitions, ", words, "]");
+  at::Tensor ctr = at::zeros({4}, like(s.window));
+  kernels::bitmapProbe(a.elemBytes, s.window.data_ptr(), a.sl, (uint32_t)sh.partitions, (uint32_t)sh.keyShift,
+                       (uint32_t)sh.bits, ptr<const uint32_t>(bitmaps), ptr<kernels::BitmapCounters>(ctr), nullptr,
+                       (uint32_t)first, cnt);
+  HIP_CHECK(hipDeviceSynchronize());
+  return bitmapCountersDict(ctr);
+}
+
+py::dict opBitmapJoin(const BitmapSide &r, const BitmapSide &s, const BitmapShape &sh) {
+  setDevice(r.window);
+  TORCH_CHECK(r.window.device() == s.window.device() && r.window.scalar_type() == s.window.scalar_type(),
+              "bitmap_join: inner and outer windows differ in device or element type");
+  bitmapTotalWords(sh.bits);
+  BitmapSideArgs a = bitmapSide(r, sh, "bitmap_join inner"), b = bitmapSide(s, sh, "bitmap_join outer");
+  at::Tensor ctr = at::zeros({4}, like(r.window));
+  kernels::bitmapJoin(a.elemBytes, r.window.data_ptr(), s.window.data_ptr(), a.sl, b.sl, (uint32_t)sh.partitions,
+                      (uint32_t)sh.keyShift, (uint32_t)sh.bits, ptr<kernels::BitmapCounters>(ctr), nullptr,
+                      kernels::MailboxArgs());
+  HIP_CHECK(hipDeviceSynchronize());
+  return bitmapCountersDict(ctr);
 }
 
 at::Tensor opScan(const at::Tensor &in) {
@@ -1549,7 +1737,50 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("bits"), py::arg("wide") = false);
   ops.def("build_probe", &opBuildProbe, py::arg("R"), py::arg("S"), py::arg("part_r"), py::arg("part_s"),
           py::arg("frag_shift"), py::arg("key_shift"), py::arg("wide") = false, py::arg("materialize") = false,
-          py::arg("r_chunk") = 4096, py::arg("s_chunk") = 65536, py::arg("out_capacity") = 0);
+          py::arg("r_chunk") = 4096, py::arg("s_chunk") = 65536, py::arg("out_capacity") = 0,
+          py::arg("frag_bits") = 0);
+  // The three LDS bitmap kernels on windows and slices the caller lays out
+  // (device only, plain counters: no mailbox).
+  using OptT = c10::optional<at::Tensor>;
+  ops.def("bitmap_words", &bitmapTotalWords, py::arg("bits"),
+          "u32 words of one partition's bitmap (both pieces of a 21-bit one)");
+  ops.def(
+      "bitmap_build",
+      [](const at::Tensor &window, int64_t partitions, int64_t bits, OptT start, OptT cur, OptT end, OptT segStart,
+         OptT segLen, int64_t keyShift, int64_t threads, int64_t flat, OptT roundMeta, int64_t first, int64_t count) {
+        return opBitmapBuild(BitmapSide{window, start, cur, end, segStart, segLen},
+                             BitmapShape{partitions, keyShift, bits, threads, flat, roundMeta}, first, count);
+      },
+      py::arg("window"), py::arg("partitions"), py::arg("bits"), py::arg("start") = py::none(),
+      py::arg("cur") = py::none(), py::arg("end") = py::none(), py::arg("seg_start") = py::none(),
+      py::arg("seg_len") = py::none(), py::arg("key_shift") = 0, py::arg("threads") = 0, py::arg("flat") = -1,
+      py::arg("round_meta") = py::none(), py::arg("first") = 0, py::arg("count") = -1);
+  ops.def(
+      "bitmap_probe",
+      [](const at::Tensor &window, const at::Tensor &bitmaps, int64_t partitions, int64_t bits, OptT start, OptT cur,
+         OptT end, OptT segStart, OptT segLen, int64_t keyShift, int64_t threads, int64_t flat, OptT roundMeta,
+         int64_t first, int64_t count) {
+        return opBitmapProbe(BitmapSide{window, start, cur, end, segStart, segLen}, bitmaps,
+                             BitmapShape{partitions, keyShift, bits, threads, flat, roundMeta}, first, count);
+      },
+      py::arg("window"), py::arg("bitmaps"), py::arg("partitions"), py::arg("bits"), py::arg("start") = py::none(),
+      py::arg("cur") = py::none(), py::arg("end") = py::none(), py::arg("seg_start") = py::none(),
+      py::arg("seg_len") = py::none(), py::arg("key_shift") = 0, py::arg("threads") = 0, py::arg("flat") = -1,
+      py::arg("round_meta") = py::none(), py::arg("first") = 0, py::arg("count") = -1);
+  ops.def(
+      "bitmap_join",
+      [](const at::Tensor &r, const at::Tensor &s, int64_t partitions, int64_t bits, OptT rStart, OptT rCur, OptT rEnd,
+         OptT sStart, OptT sCur, OptT sEnd, OptT rSegStart, OptT rSegLen, OptT sSegStart, OptT sSegLen,
+         int64_t keyShift, int64_t threads, int64_t flat, OptT roundMeta) {
+        return opBitmapJoin(BitmapSide{r, rStart, rCur, rEnd, rSegStart, rSegLen},
+                            BitmapSide{s, sStart, sCur, sEnd, sSegStart, sSegLen},
+                            BitmapShape{partitions, keyShift, bits, threads, flat, roundMeta});
+      },
+      py::arg("r"), py::arg("s"), py::arg("partitions"), py::arg("bits"), py::arg("r_start") = py::none(),
+      py::arg("r_cur") = py::none(), py::arg("r_end") = py::none(), py::arg("s_start") = py::none(),
+      py::arg("s_cur") = py::none(), py::arg("s_end") = py::none(), py::arg("r_seg_start") = py::none(),
+      py::arg("r_seg_len") = py::none(), py::arg("s_seg_start") = py::none(), py::arg("s_seg_len") = py::none(),
+      py::arg("key_shift") = 0, py::arg("threads") = 0, py::arg("flat") = -1, py::arg("round_meta") = py::none());
   ops.def("build_probe_marks", &opBuildProbeMarks, py::arg("R"), py::arg("S"), py::arg("part_r"), py::arg("part_s"),
           py::arg("frag_shift"), py::arg("key_shift"), py::arg("wide") = false, py::arg("r_chunk") = 4096,
           py::arg("s_chunk") = 65536);

@@ -157,3 +157,151 @@ def ref_join_count(r_keys, s_keys):
     idx = idx.clamp(max=uk.numel() - 1)
     hit = uk[idx] == s_keys
     return int(cnt[idx][hit].sum().item())
+
+
+# ---- selective inner key sets (test_bitmap_kernels.py, test_selective_inner.py)
+# A key of [0, D) is (fragment << network_bits) | digit: the network pass sends
+# it to partition `digit`, whose bitmap (or count table) is indexed by
+# `fragment`.  An inner side that holds every key sets every bit of every
+# bitmap, so a probe that tests the wrong bit, word, piece or partition still
+# counts |S|; the sets below leave gaps where such a probe lands.
+INNER_PATTERNS = ("half", "one_bit_per_word", "one_word_in_k", "even_partitions", "edges", "single")
+PIECE_PATTERNS = ("low_piece", "high_piece", "half")  # 21 fragment bits: two 2^20-bit pieces per partition
+OUTER_KINDS = ("complement", "same", "uniform")
+
+
+def inner_keys(pattern, D, network_bits, seed=7, bit=5, k=3, word=1):
+    """Sorted unique int64 keys of [0, D) (D a power of two) of one pattern."""
+    keys = np.arange(D, dtype=np.int64)
+    frag, digit = keys >> network_bits, keys & ((1 << network_bits) - 1)
+    limit, F = D >> network_bits, 1 << network_bits
+    if pattern == "half":
+        return np.sort(np.random.default_rng(seed).permutation(D)[:D // 2]).astype(np.int64)
+    if pattern == "one_bit_per_word":
+        return keys[(frag & 31) == bit]
+    if pattern == "one_word_in_k":
+        return keys[((frag >> 5) % k) == word]
+    if pattern == "even_partitions":
+        return keys[(digit & 1) == 0]
+    if pattern == "low_piece":
+        return keys[frag < (1 << 20)]
+    if pattern == "high_piece":
+        return keys[frag >= (1 << 20)]
+    if pattern == "edges":
+        f = np.array([0, 31, 32, limit - 1], dtype=np.int64)
+        d = np.array([0, F - 1], dtype=np.int64)
+        return np.sort(((f[:, None] << network_bits) | d[None, :]).ravel())
+    if pattern == "single":
+        return np.array([D - 1], dtype=np.int64)
+    raise ValueError(pattern)
+
+
+def outer_keys(kind, inner, D, n=0, seed=11):
+    """Outer keys for a unique inner set.  complement: every key outside it (count 0, or 1 when the inner set
+    holds D - 1: that key is always carried, so the planned key width is the pattern's own only for `same`);
+    same: the inner keys permuted (count |R|); uniform: n seeded draws with repeats over [0, D)."""
+    rng = np.random.default_rng(seed)
+    if kind == "complement":
+        mask = np.ones(D, dtype=bool)
+        mask[inner] = False
+        mask[D - 1] = True
+        return rng.permutation(np.flatnonzero(mask)).astype(np.int64)
+    if kind == "same":
+        return rng.permutation(inner).astype(np.int64)
+    if kind == "uniform":
+        out = rng.integers(0, D, size=n or D // 2, dtype=np.int64)
+        out[0] = D - 1
+        return out
+    raise ValueError(kind)
+
+
+def key_tuples(keys, device="cpu", rid0=0):
+    """[n, 2] int64 (key, rid) tensor for Relation.from_tensor."""
+    k = torch.from_numpy(np.array(keys, dtype=np.int64))  # a copy: the shared key sets stay read-only
+    return torch.stack([k, torch.arange(rid0, rid0 + k.numel(), dtype=torch.int64)], 1).contiguous().to(device)
+
+
+# ---- numpy reference of the LDS bitmap kernels (kernels/bitmap_join.hip) ------
+BITMAP_MAX_BITS = 20
+
+
+def bitmap_words(bits):
+    """u32 words of one partition's bitmap: 2^bits bits, at least 4 words; 21 bits are two 2^20-bit pieces."""
+    split = max(bits - BITMAP_MAX_BITS, 0)
+    return (1 << (bits - split - 5) if bits - split > 7 else 4) << split
+
+
+def claim_slices(start, cur, end):
+    """[groups, F] claim slices -> flat (partition, begin, length) and whether any cur > end (overflow)."""
+    start, cur, end = (np.asarray(x, dtype=np.int64) for x in (start, cur, end))
+    part = np.broadcast_to(np.arange(start.shape[1], dtype=np.int64), start.shape)
+    return part.ravel(), start.ravel(), (np.minimum(cur, end) - start).ravel(), bool((cur > end).any())
+
+
+def table_slices(seg_start, seg_len):
+    """[F, groups] segment table -> flat (partition, begin, length); a table cannot overflow."""
+    seg_start, seg_len = np.asarray(seg_start, dtype=np.int64), np.asarray(seg_len, dtype=np.int64)
+    part = np.broadcast_to(np.arange(seg_start.shape[0], dtype=np.int64)[:, None], seg_start.shape)
+    return part.ravel(), seg_start.ravel(), seg_len.ravel(), False
+
+
+def slice_fragments(window, slices, key_shift=0, round_map=(0, 0, 0)):
+    """(partition, fragment) of every element the slices hold, fragments as uint64."""
+    part, begin, length, _ = slices
+    sid, slots = slice_slots(begin, length, round_map)
+    return part[sid], u64(window)[slots] >> np.uint64(key_shift)
+
+
+def bitmap_reference(window, slices, partitions, bits, key_shift=0, round_map=(0, 0, 0)):
+    """Build reference: bitmaps [partitions, bitmap_words(bits)] uint32, and the dup / overflow flags.
+    Bit f of partition d is set iff fragment f < 32 * words occurs in d; dup iff a fragment repeats inside
+    a partition or lies outside the bitmap."""
+    words = bitmap_words(bits)
+    limit = np.uint64(32 * words)
+    part, frag = slice_fragments(window, slices, key_shift, round_map)
+    inside = frag < limit
+    idx = part[inside].astype(np.uint64) * limit + frag[inside]
+    uniq = np.unique(idx)
+    w = np.zeros(partitions * words, dtype=np.uint64)
+    np.add.at(w, (uniq >> np.uint64(5)).astype(np.int64), np.uint64(1) << (uniq & np.uint64(31)))
+    assert int(w.max(initial=0)) < (1 << 32)
+    return {"bitmaps": w.astype(np.uint32).reshape(partitions, words),
+            "dup": bool((~inside).any() or uniq.size != idx.size), "overflow": slices[3]}
+
+
+def bitmap_probe_reference(bitmaps, window, slices, bits, key_shift=0, round_map=(0, 0, 0), first=0, count=None,
+                           wrong=None):
+    """(matches, popcount) of probing `bitmaps` [partitions, words] over partitions [first, first + count).
+    wrong = "all_ones" | "bit" | "word" | "partition": what a kernel computes that sets every bit, tests
+    bit + 1 of the word, word + 1 of the bitmap (the last word: word - 1), or partition ^ 1's bitmap (the sharpness check)."""
+    bm = np.ascontiguousarray(bitmaps, dtype=np.uint32)
+    P, words = bm.shape
+    assert words == bitmap_words(bits)
+    count = P - first if count is None else count
+    limit = np.uint64(32 * words)
+    part, frag = slice_fragments(window, slices, key_shift, round_map)
+    keep = (part >= first) & (part < first + count) & (frag < limit)
+    part, frag = part[keep], frag[keep]
+    if wrong == "bit":
+        frag = (frag & ~np.uint64(31)) | ((frag + np.uint64(1)) & np.uint64(31))
+    elif wrong == "word":
+        frag = np.where(frag + np.uint64(32) < limit, frag + np.uint64(32), frag - np.uint64(32))  # last word: w - 1
+    elif wrong == "partition":
+        part = np.minimum(part ^ 1, P - 1)
+    word = bm[part, (frag >> np.uint64(5)).astype(np.int64)].astype(np.uint64)
+    hit = (word >> (frag & np.uint64(31))) & np.uint64(1)
+    if wrong == "all_ones":
+        hit = np.ones_like(hit)
+    sel = bm[first:first + count].view(np.uint8)
+    return int(hit.sum()), int(np.unpackbits(sel).sum())
+
+
+def key_slices(keys, network_bits):
+    """Keys as a (window of fragments, one slice per partition) pair for the references above."""
+    keys = np.asarray(keys, dtype=np.int64)
+    F = 1 << network_bits
+    digit = keys & (F - 1)
+    order = np.argsort(digit, kind="stable")
+    cnt = np.bincount(digit, minlength=F).astype(np.int64)
+    begin = np.cumsum(cnt) - cnt
+    return (keys[order] >> network_bits), (np.arange(F, dtype=np.int64), begin, cnt, False)
