@@ -7,7 +7,9 @@
 //                                                      writes the ncclUniqueId to PATH)
 //               [--chunks C] [--net-bits B] [--local-bits B] [--materialize] [--wide]
 //               [--round-robin] [--perf-dir DIR] [--kind inner|semi|anti|left|right|full]
-//               [--inner-domain D] [--outer-domain D] [--outer-key-offset K]
+//               [--inner-domain D] [--outer-domain D] [--outer-key-offset K] [--semi-bitmap]
+// --semi-bitmap: JoinConfig::semiBitmap (--kind semi|anti on one rank: the
+// set-semantics bitmap plan; the [INFO] plan line then says bitmapSet).
 // --kind semi|anti: `matches` is the number of outer tuples with / without an
 // inner partner; --kind left|right|full: the number of result rows (the inner
 // join's pairs plus the unmatched tuples of the preserved sides).  `correct`
@@ -75,6 +77,7 @@ int main(int argc, char **argv) {
     else if (a == "--wide") cfg.format = core::TupleFormat::Wide;
     else if (a == "--round-robin") cfg.assignment = core::AssignmentPolicy::RoundRobin;
     else if (a == "--two-level-only") cfg.bitmapJoin = false;  // no single-level bitmap join (N == 1)
+    else if (a == "--semi-bitmap") cfg.semiBitmap = true;  // --kind semi|anti at N == 1: the set bitmap plan
     else if (a == "--perf-dir") perfDir = next();
     else if (a == "--inner-domain") innerDomain = std::stoull(next());
     else if (a == "--outer-domain") outerDomain = std::stoull(next());

@@ -39,9 +39,12 @@ struct Case {
   bool wire = false;  // bit-packed exchange (host twin of kernels/wire.hip)
   // semi / anti: outer rids, outer kinds: NULL-padded rows, each checked against a set oracle
   core::JoinKind kind = core::JoinKind::Inner;
+  // semi / anti on the set-semantics bitmap plan (JoinConfig::semiBitmap): one rank, the plan must be taken
+  bool semiBitmap = false;
 };
 
 bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
+  if (c.semiBitmap) ranks = 1;
   auto group = std::make_shared<comm::InProcessGroup>(ranks);
   std::vector<std::string> errors(ranks);
   std::vector<uint64_t> matches(ranks, 0), pairs(ranks, 0);
@@ -76,8 +79,14 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
       cfg.keyHashing = c.hashing;
       cfg.chunks = 2;
       cfg.wireCodec = c.wire ? core::WireCodecMode::On : core::WireCodecMode::Off;
+      cfg.semiBitmap = c.semiBitmap;
       operators::HashJoin j(&R, &S, &ctx, cfg);
+      if (c.semiBitmap && !(j.getPlan().bitmapJoin && j.getPlan().bitmapSet))
+        throw std::runtime_error("the set bitmap plan was not taken");
       operators::JoinResult res = j.run();
+      if (c.semiBitmap && !(res.bitmapJoin && res.localFallbacks == 0 && res.outputPairs == 0 &&
+                            res.outputRids == (c.materialize ? res.localMatches : 0)))
+        throw std::runtime_error("set bitmap plan: the result fields do not add up");
       matches[r] = res.globalMatches;
       pairs[r] = res.outputPairs;
       if (outerKind) {
@@ -245,6 +254,14 @@ int main(int argc, char **argv) {
        core::JoinKind::RightOuter},
       {"full_uniform_materialize", kernels::KeyDistribution::Uniform, false, true, false, core::KeyHashing::Auto, false,
        core::JoinKind::FullOuter},
+      {"semi_bitmap_zipf_rids", kernels::KeyDistribution::Zipf, false, true, false, core::KeyHashing::Auto, false,
+       core::JoinKind::Semi, true},
+      {"semi_bitmap_uniform_count", kernels::KeyDistribution::Uniform, false, false, false, core::KeyHashing::Auto,
+       false, core::JoinKind::Semi, true},
+      {"anti_bitmap_uniform_rids", kernels::KeyDistribution::Uniform, false, true, false, core::KeyHashing::Auto, false,
+       core::JoinKind::Anti, true},
+      {"anti_bitmap_zipf_count", kernels::KeyDistribution::Zipf, false, false, false, core::KeyHashing::Auto, false,
+       core::JoinKind::Anti, true},
   };
   bool ok = true;
   for (const Case &c : cases) ok = runCase(c, ranks, G) && ok;

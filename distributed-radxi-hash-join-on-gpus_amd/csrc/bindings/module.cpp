@@ -536,7 +536,9 @@ struct BitmapSideArgs {
   std::vector<at::Tensor> keep;
 };
 
-BitmapSideArgs bitmapSide(const BitmapSide &s, const BitmapShape &sh, const char *name) {
+// claimWords: an int64 window read through claim slices (the outer side of
+// bitmap_semi_rids: 16-byte loads of two words) instead of a segment table.
+BitmapSideArgs bitmapSide(const BitmapSide &s, const BitmapShape &sh, const char *name, bool claimWords = false) {
   BitmapSideArgs out;
   const at::Tensor &w = s.window;
   TORCH_CHECK(w.is_cuda() && w.dim() == 1 && w.is_contiguous() &&
@@ -550,8 +552,8 @@ BitmapSideArgs bitmapSide(const BitmapSide &s, const BitmapShape &sh, const char
   out.sl.count = (uint64_t)n;
   out.sl.threads = (uint32_t)sh.threads;
   out.sl.flat = (int32_t)sh.flat;
-  if (out.elemBytes == 4) {
-    TORCH_CHECK(s.start && s.cur && s.end && !s.segStart && !s.segLen, name, ": u32 fragments need start / cur / end");
+  if (out.elemBytes == 4 || claimWords) {
+    TORCH_CHECK(s.start && s.cur && s.end && !s.segStart && !s.segLen, name, ": claim slices need start / cur / end");
     const at::Tensor &a = *s.start, &c = *s.cur, &e = *s.end;
     for (const at::Tensor *t : {&a, &c, &e})
       TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->dim() == 2 && t->size(0) == kernels::CLAIM_GROUPS &&
@@ -685,6 +687,60 @@ py::dict opBitmapJoin(const BitmapSide &r, const BitmapSide &s, const BitmapShap
                       kernels::MailboxArgs());
   HIP_CHECK(hipDeviceSynchronize());
   return bitmapCountersDict(ctr);
+}
+
+// Set-semantics kernels (semi / anti joins): u32 inner fragments; the outer
+// side is u32 fragments (count) or 8-byte words in claim slices (rids).
+py::dict bitmapSemiDict(const at::Tensor &ctr) {
+  at::Tensor h = ctr.cpu();
+  py::dict d;
+  d["hits"] = (uint64_t)h[0].item<int64_t>();
+  d["misses"] = (uint64_t)h[1].item<int64_t>();
+  d["dup"] = (uint64_t)h[2].item<int64_t>();
+  d["overflow"] = (uint64_t)h[3].item<int64_t>();
+  return d;
+}
+
+py::dict opBitmapSemiCount(const BitmapSide &r, const BitmapSide &s, const BitmapShape &sh) {
+  setDevice(r.window);
+  TORCH_CHECK(r.window.device() == s.window.device() && r.window.scalar_type() == at::kInt &&
+                  s.window.scalar_type() == at::kInt,
+              "bitmap_semi_count: both windows must be int32 tensors of u32 fragments on one device");
+  bitmapTotalWords(sh.bits);
+  BitmapSideArgs a = bitmapSide(r, sh, "bitmap_semi_count inner"), b = bitmapSide(s, sh, "bitmap_semi_count outer");
+  TORCH_CHECK(a.sl.narrow == b.sl.narrow, "bitmap_semi_count: both sides need one cursor width");
+  at::Tensor ctr = at::zeros({4}, like(r.window, at::kLong));
+  kernels::bitmapSemiCount(ptr<const uint32_t>(r.window), ptr<const uint32_t>(s.window), a.sl, b.sl,
+                           (uint32_t)sh.partitions, (uint32_t)sh.bits, ptr<kernels::BitmapCounters>(ctr), nullptr);
+  HIP_CHECK(hipDeviceSynchronize());
+  return bitmapSemiDict(ctr);
+}
+
+py::dict opBitmapSemiRids(const BitmapSide &r, const BitmapSide &s, const BitmapShape &sh, bool anti) {
+  setDevice(r.window);
+  TORCH_CHECK(r.window.device() == s.window.device() && r.window.scalar_type() == at::kInt &&
+                  s.window.scalar_type() == at::kLong,
+              "bitmap_semi_rids: the inner window is int32 (u32 fragments), the outer int64 (8-byte words)");
+  bitmapTotalWords(sh.bits);
+  TORCH_CHECK(sh.keyShift >= 1 && sh.keyShift < 64 && sh.bits <= 64 - sh.keyShift,
+              "bitmap_semi_rids: key_shift must leave room for the fragment bits");
+  BitmapSideArgs a = bitmapSide(r, sh, "bitmap_semi_rids inner"),
+                 b = bitmapSide(s, sh, "bitmap_semi_rids outer", true);
+  TORCH_CHECK(a.sl.narrow == b.sl.narrow, "bitmap_semi_rids: both sides need one cursor width");
+  const int64_t cap = s.window.numel();  // >= the elements of all slices
+  at::Tensor rids = at::empty({cap + 1}, like(s.window, at::kLong));
+  at::Tensor cursor = at::zeros({1}, like(s.window, at::kLong));
+  at::Tensor ctr = at::zeros({4}, like(r.window, at::kLong));
+  kernels::bitmapSemiRids(ptr<const uint32_t>(r.window), ptr<const uint64_t>(s.window), a.sl, b.sl,
+                          (uint32_t)sh.partitions, (uint32_t)sh.keyShift, (uint32_t)sh.bits, anti,
+                          ptr<unsigned long long>(rids), ptr<unsigned long long>(cursor), (uint64_t)cap,
+                          ptr<kernels::BitmapCounters>(ctr), nullptr);
+  HIP_CHECK(hipDeviceSynchronize());
+  py::dict d = bitmapSemiDict(ctr);
+  const int64_t n = cursor.cpu()[0].item<int64_t>();
+  TORCH_CHECK(n >= 0 && n <= cap, "bitmap_semi_rids: the cursor ended at ", n, " of ", cap, " output slots");
+  d["rids"] = rids.narrow(0, 0, n);
+  return d;
 }
 
 at::Tensor opScan(const at::Tensor &in) {
@@ -1131,6 +1187,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readwrite("skew_split", &core::JoinConfig::skewSplit)
       .def_readwrite("direct_count", &core::JoinConfig::directCount)
       .def_readwrite("bitmap_join", &core::JoinConfig::bitmapJoin)
+      .def_readwrite("semi_bitmap", &core::JoinConfig::semiBitmap)
       .def_readwrite("replicate_bitmap", &core::JoinConfig::replicateBitmap)
       .def_readwrite("verify_exchange", &core::JoinConfig::verifyExchange)
       .def_readwrite("passes", &core::JoinConfig::passes)
@@ -1180,6 +1237,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readonly("key_mix", &core::JoinPlan::keyMix)
       .def_readonly("sampled_network", &core::JoinPlan::sampledNetwork)
       .def_readonly("bitmap_join", &core::JoinPlan::bitmapJoin)
+      .def_readonly("bitmap_set", &core::JoinPlan::bitmapSet)
       .def_readonly("bitmap_bits", &core::JoinPlan::bitmapBits)
       .def_readonly("bitmap_replicated", &core::JoinPlan::bitmapReplicated)
       .def_readonly("key_only", &core::JoinPlan::keyOnly)
@@ -1781,6 +1839,32 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       py::arg("s_cur") = py::none(), py::arg("s_end") = py::none(), py::arg("r_seg_start") = py::none(),
       py::arg("r_seg_len") = py::none(), py::arg("s_seg_start") = py::none(), py::arg("s_seg_len") = py::none(),
       py::arg("key_shift") = 0, py::arg("threads") = 0, py::arg("flat") = -1, py::arg("round_meta") = py::none());
+  ops.def(
+      "bitmap_semi_count",
+      [](const at::Tensor &r, const at::Tensor &s, int64_t partitions, int64_t bits, OptT rStart, OptT rCur, OptT rEnd,
+         OptT sStart, OptT sCur, OptT sEnd, int64_t threads, int64_t flat, OptT roundMeta) {
+        return opBitmapSemiCount(BitmapSide{r, rStart, rCur, rEnd, c10::nullopt, c10::nullopt},
+                                 BitmapSide{s, sStart, sCur, sEnd, c10::nullopt, c10::nullopt},
+                                 BitmapShape{partitions, 0, bits, threads, flat, roundMeta});
+      },
+      py::arg("r_window"), py::arg("s_window"), py::arg("partitions"), py::arg("bits"), py::arg("r_start"),
+      py::arg("r_cur"), py::arg("r_end"), py::arg("s_start"), py::arg("s_cur"), py::arg("s_end"),
+      py::arg("threads") = 0, py::arg("flat") = -1, py::arg("round_meta") = py::none(),
+      "Set-semantics bitmap join, count only: {hits, misses, dup, overflow} (SEMI = hits, ANTI = misses)");
+  ops.def(
+      "bitmap_semi_rids",
+      [](const at::Tensor &r, const at::Tensor &s, int64_t partitions, int64_t bits, OptT rStart, OptT rCur, OptT rEnd,
+         OptT sStart, OptT sCur, OptT sEnd, int64_t threads, int64_t flat, OptT roundMeta, int64_t keyShift,
+         bool anti) {
+        return opBitmapSemiRids(BitmapSide{r, rStart, rCur, rEnd, c10::nullopt, c10::nullopt},
+                                BitmapSide{s, sStart, sCur, sEnd, c10::nullopt, c10::nullopt},
+                                BitmapShape{partitions, keyShift, bits, threads, flat, roundMeta}, anti);
+      },
+      py::arg("r_window"), py::arg("s_window"), py::arg("partitions"), py::arg("bits"), py::arg("r_start"),
+      py::arg("r_cur"), py::arg("r_end"), py::arg("s_start"), py::arg("s_cur"), py::arg("s_end"),
+      py::arg("threads") = 0, py::arg("flat") = -1, py::arg("round_meta") = py::none(), py::arg("key_shift") = 32,
+      py::arg("anti") = false,
+      "Set-semantics bitmap join writing the qualifying outer rids: the counters plus `rids` (int64, any order)");
   ops.def("build_probe_marks", &opBuildProbeMarks, py::arg("R"), py::arg("S"), py::arg("part_r"), py::arg("part_s"),
           py::arg("frag_shift"), py::arg("key_shift"), py::arg("wide") = false, py::arg("r_chunk") = 4096,
           py::arg("s_chunk") = 65536);

@@ -155,6 +155,12 @@ struct JoinConfig {
   bool bitmapJoin = true;       // N == 1 on device, counting, sampled network pass: one LDS bitmap per network
                                 // partition instead of the local pass when the fragment range fits (unique inner
                                 // keys; a duplicate falls back to the two-level pass)
+  // Semi / anti joins at N == 1 whose key range fits the bitmaps: the single-
+  // level bitmap plan with set semantics (JoinPlan::bitmapSet).  The inner side
+  // is a set, so repeated inner keys do not matter; a count-only join carries
+  // no rids at all, a materializing one writes the qualifying outer rids from
+  // the bitmap kernel itself.  Opt-in: the default stays the mark plan.
+  bool semiBitmap = false;
   // N > 1 counting joins of unique inner keys whose key range fits bitmaps
   // (tasks/BitmapJoin): every rank builds the bitmaps of its own inner keys,
   // one RCCL all-reduce ORs them, and every rank probes its own outer tuples
@@ -215,7 +221,8 @@ struct JoinPlan {
   // whole partitions: materializing joins, and semi / anti joins (whose
   // result is per outer tuple).  Rules out the rid-free layouts (keyOnly,
   // fragments), the bitmap plans and the pipelined outer side.
-  bool carriesRids() const { return materialize || kind != JoinKind::Inner; }
+  // (The set bitmap plan of a count-only semi / anti join is rid-free too.)
+  bool carriesRids() const { return materialize || (kind != JoinKind::Inner && !bitmapSet); }
   bool keyMix = false;        // radix digits from kernels::KeyMix{keyBits} of the key
   // Counting join whose keys do not fit a CompressedTuple (sparse 63-bit keys):
   // after the network pass a tuple is the 8-byte word key >> networkBits (no
@@ -228,6 +235,7 @@ struct JoinPlan {
   bool pipelineOuter = false;   // N > 1 counting: outer local pass + build/probe per exchange chunk
   bool bitmapJoin = false;      // single-level bitmap join (kernels::bitmapJoin) after the sampled network pass
   uint32_t bitmapBits = 0;      // fragment bits per network partition (bitmap size 2^bitmapBits)
+  bool bitmapSet = false;       // bitmapJoin with set semantics: semi / anti join (JoinConfig::semiBitmap)
   bool bitmapReplicated = false;  // bitmaps all-reduced over ranks, outer probed in place (tasks/BitmapJoin)
   bool oneSided = false;          // ExchangeMode::OneSided in effect (data::Window::enableOneSided)
   // Cost model of the N > 1 plan choice: bytes one rank puts on its links per

@@ -348,6 +348,49 @@ uint64_t markCompactPairs(const kernels::BPArgs &a, const uint64_t *marks, bool 
   return n;
 }
 
+// One partition's set bitmap over the whole planned range (the device kernels
+// split 21-bit ranges over two workgroups; the host needs no pieces).
+namespace {
+template <typename E, typename Emit>
+BitmapSemiResult bitmapSemi(const uint32_t *r, const uint64_t *rBegin, const E *s, const uint64_t *sBegin,
+                            uint32_t partitions, uint32_t keyShift, uint32_t bits, Emit &&emit) {
+  BitmapSemiResult o;
+  const uint64_t range = (uint64_t)kernels::bitmapWords(std::min(bits, kernels::BITMAP_MAX_BITS)) * 32
+                         << (bits > kernels::BITMAP_MAX_BITS ? bits - kernels::BITMAP_MAX_BITS : 0);  // as the kernels
+  std::vector<uint64_t> bm((size_t)((range + 63) / 64));
+  for (uint32_t p = 0; p < partitions; ++p) {
+    std::fill(bm.begin(), bm.end(), 0);
+    for (uint64_t i = rBegin[p]; i < rBegin[p + 1]; ++i) {
+      const uint64_t f = r[i];
+      if (f >= range)
+        o.flags |= kernels::BM_FLAG_DUP;  // outside the planned range: the plan does not hold
+      else
+        bm[f >> 6] |= 1ull << (f & 63);
+    }
+    for (uint64_t i = sBegin[p]; i < sBegin[p + 1]; ++i) {
+      const uint64_t f = (uint64_t)s[i] >> keyShift;
+      const bool hit = f < range && ((bm[f >> 6] >> (f & 63)) & 1ull);
+      ++(hit ? o.hits : o.misses);
+      emit(o, s[i], hit);
+    }
+  }
+  return o;
+}
+}  // namespace
+
+BitmapSemiResult bitmapSemiCount(const uint32_t *r, const uint64_t *rBegin, const uint32_t *s, const uint64_t *sBegin,
+                                 uint32_t partitions, uint32_t bits) {
+  return bitmapSemi(r, rBegin, s, sBegin, partitions, 0, bits, [](BitmapSemiResult &, uint32_t, bool) {});
+}
+
+BitmapSemiResult bitmapSemiRids(const uint32_t *r, const uint64_t *rBegin, const uint64_t *s, const uint64_t *sBegin,
+                                uint32_t partitions, uint32_t keyShift, uint32_t bits, bool anti, uint64_t *out) {
+  const uint64_t ridMask = (1ull << keyShift) - 1;
+  return bitmapSemi(r, rBegin, s, sBegin, partitions, keyShift, bits, [&](BitmapSemiResult &o, uint64_t w, bool hit) {
+    if (hit != anti) out[o.written++] = w & ridMask;
+  });
+}
+
 uint64_t npjJoin(const data::Tuple *R, uint64_t nR, const data::Tuple *S, uint64_t nS) {
   std::unordered_map<uint64_t, uint64_t> counts;
   counts.reserve(nR * 2);

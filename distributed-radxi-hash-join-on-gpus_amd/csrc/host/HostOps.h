@@ -60,6 +60,22 @@ uint64_t buildProbeOuter(const kernels::BPArgs &a, uint64_t *marksR, uint64_t *m
 uint64_t markCompactPairs(const kernels::BPArgs &a, const uint64_t *marks, bool innerSide, ulonglong2 *out,
                           uint64_t *cursor, uint64_t outCapacity);
 
+// Set-semantics bitmap join (twins of kernels::bitmapSemiCount / bitmapSemiRids)
+// over exactly partitioned sides: partition p holds elements [begin[p],
+// begin[p + 1]).  Inner: u32 fragments; outer: u32 fragments (count) or 8-byte
+// words fragment << keyShift | rid (rids: the rid of every hit, anti: miss, is
+// appended to out, which holds one slot per outer element).  Returns the
+// BM_FLAG_* raised (an inner fragment >= 2^bits: BM_FLAG_DUP; repeats are no
+// error); outer fragments beyond the range are misses.
+struct BitmapSemiResult {
+  uint64_t hits = 0, misses = 0, written = 0;
+  uint32_t flags = 0;
+};
+BitmapSemiResult bitmapSemiCount(const uint32_t *r, const uint64_t *rBegin, const uint32_t *s, const uint64_t *sBegin,
+                                 uint32_t partitions, uint32_t bits);
+BitmapSemiResult bitmapSemiRids(const uint32_t *r, const uint64_t *rBegin, const uint64_t *s, const uint64_t *sBegin,
+                                uint32_t partitions, uint32_t keyShift, uint32_t bits, bool anti, uint64_t *out);
+
 // Wire codec (kernels.h, WireCodec) over host segment lists.
 void wirePack(const uint64_t *raw, uint64_t *wire, const kernels::WireSeg *segs, uint32_t nSegs,
               const kernels::WireCodec &c);

@@ -707,6 +707,27 @@ void bitmapBuild(uint32_t elemBytes, const void *r, const BitmapSlices &rs, uint
 void bitmapProbe(uint32_t elemBytes, const void *s, const BitmapSlices &ss, uint32_t partitions, uint32_t keyShift,
                  uint32_t bits, const uint32_t *bitmaps, BitmapCounters *out, hipStream_t st, uint32_t first = 0,
                  uint32_t count = UINT32_MAX);
+// Set-semantics bitmap join for semi / anti joins (JoinPlan::bitmapSet): the
+// build tolerates repeated inner fragments (a bitmap is a set); a fragment at
+// or beyond 2^bits still raises BM_FLAG_DUP (the plan does not hold).  Both
+// kernels have bitmapJoin's launch shape (one workgroup per partition and
+// piece, same thread and walk selection) and report hits in out->matches and
+// misses in out->popcount; every outer element is one or the other exactly
+// once (piece 0 owns outer fragments beyond the range: misses), so hits +
+// misses = |S| whenever no slice overflowed.  SEMI = hits, ANTI = misses.
+// r, s: u32 fragments in claim slices of one cursor width.
+void bitmapSemiCount(const uint32_t *r, const uint32_t *s, const BitmapSlices &rs, const BitmapSlices &ss,
+                     uint32_t partitions, uint32_t bits, BitmapCounters *out, hipStream_t st,
+                     const MailboxArgs &mb = MailboxArgs());
+// s: 8-byte CompressedTuples (fragment << keyShift | rid) in claim slices
+// (start / cur / end, optional roundMeta of the 8-byte window; slices start on
+// even positions).  rids[0, *cursor) = the rid of every hit (anti: miss), each
+// once, in no particular order; *cursor is zeroed by the caller and ends at
+// their count; positions at or beyond `capacity` are counted, not written.
+void bitmapSemiRids(const uint32_t *r, const uint64_t *s, const BitmapSlices &rs, const BitmapSlices &ss,
+                    uint32_t partitions, uint32_t keyShift, uint32_t bits, bool anti, unsigned long long *rids,
+                    unsigned long long *cursor, uint64_t capacity, BitmapCounters *out, hipStream_t st,
+                    const MailboxArgs &mb = MailboxArgs());
 
 // ------------------------------------------------------------ wire codec
 // Exchange wire format for 8-byte CompressedTuples (N > 1).  On the wire a

@@ -71,6 +71,16 @@ static double spillFixedBytes(uint64_t avail) { return std::min<double>(256.0 * 
 void HashJoin::planPasses() {
   uint32_t K = config.passes;
   const uint64_t n[2] = {innerRelation->getLocalSize(), outerRelation->getLocalSize()};
+  if (plan.bitmapSet && plan.materialize && ctx->onDevice() && config.reserveWorkspace) {
+    // A materializing set plan has no partition-group passes (its rid list is
+    // one buffer): when its workspace does not fit, the join runs on the mark
+    // plan, as without JoinConfig::semiBitmap.
+    size_t freeB = 0, totalB = 0;
+    HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
+    uint64_t avail = (uint64_t)(freeB * 0.85);
+    if (config.workspaceBudget) avail = std::min<uint64_t>(avail, config.workspaceBudget);
+    if (workspaceEstimate() > avail) plan = basePlan;
+  }
   if (K == 0) {
     K = 1;
     // Materializing joins spill only into a host output buffer (the pairs of
@@ -88,7 +98,7 @@ void HashJoin::planPasses() {
       const uint64_t est = workspaceEstimate(), tuplesB = (n[0] + n[1]) * sizeof(data::Tuple);
       spill.estimate = est;
       spill.available = avail;
-      if (est > avail && plan.bitmapJoin && numberOfNodes == 1) {
+      if (est > avail && plan.bitmapJoin && numberOfNodes == 1 && !plan.materialize) {
         // The bitmap plan spills by partition groups instead (tasks/BitmapJoin):
         // each group pass reads both relations once and writes only the
         // fragments of its network partitions -- no pass buffers, no
@@ -521,6 +531,14 @@ std::vector<uint64_t> HashJoin::workspaceParts() const {
   if (plan.bitmapJoin) {
     // u32 fragments in claim slices (round-interleaved unless a partition-group pass)
     const uint32_t lp = plan.groupBudget ? 0 : kernels::roundLpFor(plan.roundLp, 4);
+    if (plan.bitmapSet && plan.materialize) {
+      // Set plan with rids: u32 inner fragments, 8-byte outer CompressedTuples
+      // (pieces of the same bytes), and one rid per outer tuple.
+      parts.push_back((sampledCap(n[0], lp) + 64) * 4);
+      parts.push_back((sampledCap(n[1], kernels::roundLpFor(plan.roundLp, 8)) + 64) * 8);
+      parts.push_back((n[1] + 2) * 8);
+      return parts;
+    }
     for (int r = 0; r < 2; ++r) parts.push_back((sampledCap(n[r], lp) + 64) * 4);
     if (plan.bitmapReplicated) parts.push_back(2ull * F * kernels::bitmapWords(plan.bitmapBits) * 4);
     return parts;
@@ -615,6 +633,7 @@ std::vector<uint64_t> HashJoin::workspaceParts() const {
 void HashJoin::planBitmap() {
   const uint32_t N = numberOfNodes;
   plan.bitmapJoin = false;
+  plan.bitmapSet = false;
   plan.bitmapReplicated = false;
   const double perPeer = config.linkGBpsPerPeer > 0 ? config.linkGBpsPerPeer : kDefaultLinkGBpsPerPeer;
   plan.linkGBps = N > 1 ? perPeer * (double)std::min<uint32_t>(N - 1, 7) : 0.0;
@@ -626,11 +645,19 @@ void HashJoin::planBitmap() {
                             ((double)innerRelation->getGlobalSize() * wR + (double)outerRelation->getGlobalSize() * wS) /
                             8.0 / std::max<uint32_t>(N, 1);
   }
-  if (!config.bitmapJoin || plan.carriesRids() || plan.wide || plan.keyOnly || plan.keyBits >= 64) return;
-  // Repeated inner keys would only make the bitmap plan fall back after a
-  // whole failed join; replicateBitmap = On still forces it (tests of that
-  // fallback path).
-  if (plan.innerRepeats && config.replicateBitmap != core::PlanChoice::On) return;
+  // Set plan (JoinConfig::semiBitmap): semi / anti joins on one rank.  A bitmap
+  // is a set, as the inner side of these kinds is: repeated inner keys do not
+  // block it, and a count-only join carries no rids.  (N > 1: the replicated
+  // plan's all-reduce is a sum, an OR only for keys unique across ranks.)
+  const bool set = config.semiBitmap && core::isRidKind(plan.kind) && N == 1;
+  if (plan.wide || plan.keyOnly || plan.keyBits >= 64) return;
+  if (!set) {
+    if (!config.bitmapJoin || plan.carriesRids()) return;
+    // Repeated inner keys would only make the bitmap plan fall back after a
+    // whole failed join; replicateBitmap = On still forces it (tests of that
+    // fallback path).
+    if (plan.innerRepeats && config.replicateBitmap != core::PlanChoice::On) return;
+  }
   const uint32_t want = plan.keyBits > kernels::BITMAP_MAX_BITS ? plan.keyBits - kernels::BITMAP_MAX_BITS : 0;
   const uint32_t nb =
       config.networkBits ? config.networkBits : std::min<uint32_t>(kernels::MAX_PART_BITS, std::max<uint32_t>(10, want));
@@ -640,10 +667,15 @@ void HashJoin::planBitmap() {
   // travel whole, 256 KiB per partition).
   const uint32_t maxBits = kernels::BITMAP_MAX_BITS + kernels::BITMAP_MAX_SPLIT;
   if (bits > maxBits || !kernels::fragWordFits(plan.keyBits, nb)) return;
+  // Materializing set plan: the outer CompressedTuple holds fragment and rid
+  // (makePlan made keyShift >= the rid bits).
+  if (set && plan.materialize && (plan.keyShift < 32 || plan.keyShift >= 64 || bits > 64 - plan.keyShift)) return;
   const double bitmapBytes = (double)(1ull << nb) * kernels::bitmapWords(bits) * 4;
   plan.replicatedLinkBytes = N > 1 ? 2.0 * (N - 1) / N * bitmapBytes : 0.0;
   bool use;
-  if (N == 1)
+  if (set)
+    use = true;  // device and host engine alike: the host path is the plan's reference
+  else if (N == 1)
     use = ctx->onDevice() || config.replicateBitmap == core::PlanChoice::On;
   else if (config.replicateBitmap == core::PlanChoice::On)
     use = true;
@@ -655,6 +687,7 @@ void HashJoin::planBitmap() {
   plan.networkBits = nb;
   plan.bitmapJoin = true;
   plan.bitmapBits = bits;
+  plan.bitmapSet = set;
   plan.bitmapReplicated = N > 1;
   plan.sampledNetwork = !bitmapExact;
 }
@@ -820,11 +853,17 @@ JoinResult HashJoin::runImpl() {
   run.t0 = nowUs();
   if (dev) HIP_CHECK(hipEventRecord(ev[0], ctx->stream()));
   if (plan.bitmapJoin) {
-    if (BitmapPlan(env, bitmapExact).run(run.t0, result)) {
+    BitmapPlan bitmap(env, bitmapExact);
+    if (bitmap.run(run.t0, result)) {
+      output = nullptr;
+      outputRids = bitmap.outputRids();  // set plan, materializing; null otherwise
+      outputEpoch = ctx->workspace().epoch();
       RESULT_COUNTER = result.localMatches;
       return result;
     }
-    plan = basePlan;  // a repeated inner key: this and every later join on the two-level plan
+    // A repeated inner key (set plan: an inner key beyond the planned range):
+    // this and every later join on the two-level plan.
+    plan = basePlan;
     ++result.localFallbacks;
     JOIN_DEBUG("HashJoin", "bitmap join: repeated inner key -> %s", plan.describe().c_str());
   }

@@ -334,6 +334,10 @@ bool BitmapPlan::run(uint64_t t0, JoinResult &r) {
   r.sampledNetwork = !exact;
   r.localMatches = o.localMatches;
   r.globalMatches = o.globalMatches;
+  if (plan.bitmapSet && plan.materialize) {  // semi / anti: outer rids, no pairs
+    rids = o.rids;
+    r.outputRids = o.localMatches;
+  }
   r.buildProbeItems = 1ull << plan.networkBits;
   r.innerReceived = env.inner->getLocalSize();
   r.outerReceived = env.outer->getLocalSize();

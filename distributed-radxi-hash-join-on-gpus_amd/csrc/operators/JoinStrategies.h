@@ -152,9 +152,13 @@ class BitmapPlan {
   BitmapPlan(JoinEnv &env, bool &exact) : env(env), exact(exact) {}
   // false: a repeated inner key (the caller continues on the two-level plan).
   bool run(uint64_t t0, JoinResult &r);
+  // Set plan, materializing: the qualifying outer rids of the last run
+  // (r.outputRids of them, in the engine's workspace).
+  const uint64_t *outputRids() const { return rids; }
 
  private:
   JoinEnv &env;
+  const uint64_t *rids = nullptr;
   bool &exact;  // sticky: exact histograms (small inputs, or after an overflow)
 };
 

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../comm/Communicator.h"
+#include "../host/HostOps.h"
 #include "../memory/Arena.h"
 #include "../performance/Clock.h"
 #include "../performance/Measurements.h"
@@ -27,7 +28,13 @@ BitmapJoin::BitmapJoin(data::Relation *innerRelation, data::Relation *outerRelat
                        const core::JoinPlan &plan, uint32_t maxBlocks, uint32_t sampleStride, hipEvent_t *ev)
     : inner(innerRelation), outer(outerRelation), ctx(ctx), plan(plan), maxBlocks(maxBlocks),
       sampleStride(std::max<uint32_t>(1, sampleStride)), ev(ev) {
-  JOIN_ASSERT(plan.bitmapJoin && !plan.materialize && !plan.wide, "BitmapJoin", "needs a counting bitmap plan");
+  JOIN_ASSERT(plan.bitmapJoin && (!plan.materialize || plan.bitmapSet) && !plan.wide, "BitmapJoin",
+              "needs a counting bitmap plan (or a set plan)");
+  JOIN_ASSERT(!plan.bitmapSet || (core::isRidKind(plan.kind) && ctx->numberOfNodes() == 1), "BitmapJoin",
+              "the set plan answers semi / anti joins on one rank");
+  JOIN_ASSERT(!(plan.bitmapSet && plan.materialize) || (plan.keyShift >= 32 && plan.bitmapBits <= 64 - plan.keyShift),
+              "BitmapJoin", "%u fragment bits above keyShift=%u do not fit a CompressedTuple", plan.bitmapBits,
+              plan.keyShift);
   JOIN_ASSERT(plan.bitmapBits <= kernels::BITMAP_MAX_BITS + kernels::BITMAP_MAX_SPLIT, "BitmapJoin",
               "%u fragment bits do not fit a bitmap", plan.bitmapBits);
   JOIN_ASSERT(kernels::fragWordFits(plan.keyBits, plan.networkBits), "BitmapJoin",
@@ -40,7 +47,7 @@ BitmapJoin::Outcome BitmapJoin::run(bool exact) { return ctx->onDevice() ? runDe
 // functions of the sizes, but their host loops (every block and sampled tile)
 // took ~20 us per join in front of the first kernel, so they are computed
 // once per thread (in-process ranks are threads) and size.
-const BitmapJoin::SidePlan &BitmapJoin::sidePlan(uint64_t n, bool exact, uint32_t stride) const {
+const BitmapJoin::SidePlan &BitmapJoin::sidePlan(uint64_t n, bool exact, uint32_t stride, uint32_t elemBytes) const {
   struct Key {
     uint64_t n;
     uint32_t maxBlocks, bits, stride, lp;
@@ -52,7 +59,8 @@ const BitmapJoin::SidePlan &BitmapJoin::sidePlan(uint64_t n, bool exact, uint32_
   };
   thread_local std::map<Key, SidePlan> cache;
   const uint32_t F = 1u << plan.networkBits;
-  const Key k{n, maxBlocks, plan.networkBits, stride, plan.roundLp, exact};
+  const uint32_t lp = kernels::roundLpFor(plan.roundLp, elemBytes);
+  const Key k{n, maxBlocks, plan.networkBits, stride, lp, exact};
   auto it = cache.find(k);
   if (it != cache.end()) return it->second;
   if (cache.size() > 64) cache.clear();
@@ -60,15 +68,15 @@ const BitmapJoin::SidePlan &BitmapJoin::sidePlan(uint64_t n, bool exact, uint32_
   sp.geom = kernels::partitionGeometry(n, maxBlocks);
   sp.stride = exact ? 1 : kernels::sampleStrideFor(sp.geom, n, F, stride);
   sp.sc = kernels::sampleScale(sp.geom, n, sp.stride, exact);
-  sp.cap = kernels::sampledWindowCapacity(sp.sc, F, kernels::roundLpFor(plan.roundLp, 4));
+  sp.cap = kernels::sampledWindowCapacity(sp.sc, F, lp);
   return cache.emplace(k, sp).first->second;
 }
 
 // Sampled (or exact) histogram -> device layout of bounded claim slices ->
 // bounded claim scatter of u32 fragments.  Nothing here waits for the device.
-bool BitmapJoin::sideNarrow(data::Relation *r, bool exact) const {
+bool BitmapJoin::sideNarrow(data::Relation *r, bool exact, uint32_t elemBytes) const {
   const uint64_t n = r->getLocalSize();
-  return kernels::cursorsNarrow(sidePlan(n, exact, sampleStride).cap + n);
+  return kernels::cursorsNarrow(sidePlan(n, exact, sampleStride, elemBytes).cap + n);
 }
 
 // Sampled (or exact) totals and the device layout of the bounded claim
@@ -90,7 +98,7 @@ void BitmapJoin::layoutSides(Side *sides, uint32_t count, bool exact, bool narro
   for (uint32_t i = 0; i < count; ++i) {
     Side &s = sides[i];
     const uint64_t n = s.relation->getLocalSize();
-    const SidePlan &sp = sidePlan(n, exact, sampleStride);
+    const SidePlan &sp = sidePlan(n, exact, sampleStride, s.elemBytes);
     s.geom = sp.geom;
     const uint32_t stride = sp.stride;
     sampled = sampled && stride > 1;
@@ -111,7 +119,7 @@ void BitmapJoin::layoutSides(Side *sides, uint32_t count, bool exact, bool narro
       kernels::netHistogram(in[i].data, in[i].n, bits, in[i].geom, blockHist, st, mix, 1);
       kernels::netGroupTotals(blockHist, F, in[i].geom.blocks, in[i].totals, st);
       if (in[i].stride > 1) {  // sampled side next to an exact one: its scale counts every tile now
-        const SidePlan &one = sidePlan(in[i].n, exact, 1);
+        const SidePlan &one = sidePlan(in[i].n, exact, 1, sides[i].elemBytes);
         lay[i].sc = one.sc;
         sides[i].cap = one.cap;
       }
@@ -120,10 +128,10 @@ void BitmapJoin::layoutSides(Side *sides, uint32_t count, bool exact, bool narro
   const size_t cb = narrow ? 4 : 8;
   // Round-interleaved fragment windows (kernels::RoundMap): the slots follow
   // from the layout kernel's map, which every reader takes from roundMeta.
-  const uint32_t lp = kernels::roundLpFor(plan.roundLp, 4);
   uint32_t lns = 0;
   while ((1u << lns) < G * F) ++lns;
   for (uint32_t i = 0; i < count; ++i) {
+    const uint32_t lp = kernels::roundLpFor(plan.roundLp, sides[i].elemBytes);  // pieces of the same bytes
     lay[i].gstart = ws.get((size_t)G * F * cb);
     lay[i].gcur = ws.get((size_t)G * F * cb);
     lay[i].gend = ws.get((size_t)G * F * cb);
@@ -149,7 +157,7 @@ void BitmapJoin::layoutSides(Side *sides, uint32_t count, bool exact, bool narro
     s.slices.threads = plan.variants.bmThreads;
     s.slices.flat = plan.variants.bmFlat;
     s.slices.roundMeta = lay[i].roundMeta;
-    s.frags = ws.getArray<uint32_t>(std::max<uint64_t>(s.cap, 16));
+    s.frags = static_cast<uint32_t *>(ws.get(std::max<uint64_t>(s.cap, 16) * s.elemBytes));
   }
   kernels::netSampledLayout(lay, count, F, narrow, st);
 }
@@ -157,6 +165,13 @@ void BitmapJoin::layoutSides(Side *sides, uint32_t count, bool exact, bool narro
 // The bounded claim scatter of one side's u32 fragments into its slices.
 void BitmapJoin::scatterSide(Side &s) {
   const kernels::KeyMix mix{plan.keyMix ? 1u : 0u, plan.keyBits};
+  if (s.elemBytes == 8) {  // CompressedTuples (fragment << keyShift | rid) into the same bounded claim slices
+    kernels::netScatter(s.relation->getData(), s.relation->getLocalSize(), plan.networkBits, plan.keyShift, s.geom, 0,
+                        s.geom.blocks, const_cast<void *>(s.slices.cur), reinterpret_cast<uint64_t *>(s.frags),
+                        ctx->stream(), plan.keyBits, mix, s.slices.end, s.slices.narrow ? 1 : 0, true,
+                        s.slices.roundMeta);
+    return;
+  }
   kernels::netScatterFrag(s.relation->getData(), s.relation->getLocalSize(), plan.networkBits, s.geom, 0,
                           s.geom.blocks, const_cast<void *>(s.slices.cur), s.frags, ctx->stream(), plan.keyBits, mix,
                           s.slices.end, s.slices.narrow ? 1 : 0, s.slices.roundMeta);
@@ -302,7 +317,10 @@ BitmapJoin::Outcome BitmapJoin::runDeviceGroups(bool exact) {
       utils::faultPoint("local");
       utils::faultPoint("build_probe");
     }
-    kernels::bitmapJoin(4, both[0].frags, both[1].frags, both[0].slices, both[1].slices, g.n, 0, bits, cnt, st);
+    if (plan.bitmapSet)  // hits and misses accumulate over the passes
+      kernels::bitmapSemiCount(both[0].frags, both[1].frags, both[0].slices, both[1].slices, g.n, bits, cnt, st);
+    else
+      kernels::bitmapJoin(4, both[0].frags, both[1].frags, both[0].slices, both[1].slices, g.n, 0, bits, cnt, st);
   }
   HIP_CHECK(hipEventRecord(ev[4], st));
   tl.beginAt("BPTASKTIME", ev[2]);
@@ -326,12 +344,19 @@ BitmapJoin::Outcome BitmapJoin::runDeviceGroups(bool exact) {
   o.devJoinMs = ms;
   o.localMatches = res->matches;
   o.popcount = res->popcount;
+  if (plan.bitmapSet) {
+    o.popcount = 0;
+    if (!res->overflow && !res->dup) finishSet(o, res->matches, res->popcount);
+  }
   agree(o, (res->dup ? kernels::BM_FLAG_DUP : 0u) | (res->overflow ? kernels::BM_FLAG_OVERFLOW : 0u));
   return o;
 }
 
 BitmapJoin::Outcome BitmapJoin::runDevice(bool exact) {
-  if (plan.groupBudget && ctx->numberOfNodes() == 1) return runDeviceGroups(exact);
+  if (plan.groupBudget && ctx->numberOfNodes() == 1) {
+    JOIN_ASSERT(!plan.materialize, "BitmapJoin", "partition-group passes are count-only");
+    return runDeviceGroups(exact);
+  }
   const uint32_t F = 1u << plan.networkBits, N = ctx->numberOfNodes(), bits = plan.bitmapBits;
   const hipStream_t st = ctx->stream();
   memory::Arena &ws = ctx->workspace();
@@ -350,12 +375,22 @@ BitmapJoin::Outcome BitmapJoin::runDevice(bool exact) {
   Outcome o;
   // One cursor width for both sides (the fused N = 1 kernel reads both with
   // one slice type; e.g. 1B inner x 4B outer needs 8-byte cursors on both).
-  const bool narrowOk = sideNarrow(inner, exact) && sideNarrow(outer, exact);
+  const bool setRids = plan.bitmapSet && plan.materialize;
+  const uint32_t outerBytes = setRids ? 8 : 4;
+  const bool narrowOk = sideNarrow(inner, exact) && sideNarrow(outer, exact, outerBytes);
   // Time points (one event each, shared by the spans that meet there):
   // ev[0] join start, ev[1] inner side partitioned, ev[2] outer side
   // partitioned, ev[3] probe start (N > 1: after the all-reduce), ev[4] end.
   performance::Timeline &tl = ctx->timeline();
   Side both[2] = {Side{inner, {}, nullptr, {}}, Side{outer, {}, nullptr, {}}};
+  both[1].elemBytes = outerBytes;
+  unsigned long long *ridOut = nullptr, *ridCursor = nullptr;
+  const uint64_t ridCapacity = outer->getLocalSize();
+  if (setRids) {  // one rid per outer tuple at most: the output cannot overflow
+    ridOut = ws.getArray<unsigned long long>(ridCapacity + 1);
+    ridCursor = ws.getArray<unsigned long long>(1);
+    ctx->zero(ridCursor, sizeof(unsigned long long));
+  }
   {
     performance::TraceRange tr("bitmap_network_inner");
     utils::faultPoint("network");
@@ -389,7 +424,14 @@ BitmapJoin::Outcome BitmapJoin::runDevice(bool exact) {
     mb.arrivals = &ctx->control()->arrivals;
     mb.seq = ctx->nextMailboxSeq();
     mailboxSeq = mb.seq;
-    kernels::bitmapJoin(4, ri.frags, ro.frags, ri.slices, ro.slices, F, 0, bits, cnt, st, mb);
+    if (setRids)
+      kernels::bitmapSemiRids(ri.frags, reinterpret_cast<const uint64_t *>(ro.frags), ri.slices, ro.slices, F,
+                              plan.keyShift, bits, plan.kind == core::JoinKind::Anti, ridOut, ridCursor, ridCapacity,
+                              cnt, st, mb);
+    else if (plan.bitmapSet)
+      kernels::bitmapSemiCount(ri.frags, ro.frags, ri.slices, ro.slices, F, bits, cnt, st, mb);
+    else
+      kernels::bitmapJoin(4, ri.frags, ro.frags, ri.slices, ro.slices, F, 0, bits, cnt, st, mb);
     HIP_CHECK(hipEventRecord(ev[4], st));
     tl.endAt("BPKERNEL", ev[4]);
     tl.endAt("BPTASKTIME", ev[4]);
@@ -456,6 +498,11 @@ BitmapJoin::Outcome BitmapJoin::runDevice(bool exact) {
   // back[0]: this rank's counters; back[1] (N > 1): all ranks' sums, combined
   // on the device behind the probe (one synchronisation per join).
   BitmapCounters *back = ctx->staging().getArray<BitmapCounters>(2);
+  unsigned long long *ridCountBack = nullptr;
+  if (setRids) {  // the final cursor: read back behind the kernel, awaited by the synchronize below
+    ridCountBack = ctx->staging().getArray<unsigned long long>(1);
+    ctx->readBack(ridCountBack, ridCursor, sizeof(unsigned long long));
+  }
   const uint64_t tEnqueued = performance::nowUs();
   if (useControl) {
     // The kernel's last wave published the counters: spin on the mailbox,
@@ -497,9 +544,32 @@ BitmapJoin::Outcome BitmapJoin::runDevice(bool exact) {
     o.overflow = back[1].overflow > 0;
     if (!o.overflow && o.popcount != inner->getGlobalSize()) o.dup = true;
   } else {
+    if (plan.bitmapSet) {
+      o.popcount = 0;
+      if (!back[0].overflow && !back[0].dup) {
+        finishSet(o, back[0].matches, back[0].popcount);
+        if (setRids) {
+          JOIN_ASSERT(*ridCountBack == o.localMatches, "BitmapJoin",
+                      "the set bitmap kernel wrote %llu rids for %llu qualifying outer tuples", *ridCountBack,
+                      (unsigned long long)o.localMatches);
+          o.rids = reinterpret_cast<const uint64_t *>(ridOut);
+        }
+      }
+    }
     agree(o, (back[0].dup ? kernels::BM_FLAG_DUP : 0u) | (back[0].overflow ? kernels::BM_FLAG_OVERFLOW : 0u));
   }
   return o;
+}
+
+// Every outer tuple is a hit or a miss exactly once (whenever no slice
+// overflowed): anything else is a kernel bug, not a reason to fall back.
+void BitmapJoin::finishSet(Outcome &o, uint64_t hits, uint64_t misses) const {
+  JOIN_ASSERT(hits + misses == outer->getLocalSize(), "BitmapJoin",
+              "set bitmap join: %lu hits + %lu misses over %lu outer tuples", (unsigned long)hits,
+              (unsigned long)misses, (unsigned long)outer->getLocalSize());
+  o.hits = hits;
+  o.misses = misses;
+  o.localMatches = plan.kind == core::JoinKind::Anti ? misses : hits;
 }
 
 // Host reference of the same plan (CPU tests of the N-rank logic): exact
@@ -526,6 +596,57 @@ BitmapJoin::Outcome BitmapJoin::runHost() {
   std::vector<uint32_t> rf, sf;
   std::vector<uint64_t> rb, sb;
   performance::Timeline &tl = ctx->timeline();
+  if (plan.bitmapSet) {
+    // Set mode: the host twins of the set kernels over exact partitions; the
+    // outer side keeps its rids (8-byte CompressedTuples) when materializing.
+    const bool withRids = plan.materialize;
+    std::vector<uint64_t> sw;
+    utils::faultPoint("network");
+    tl.begin("MIMAINPART");
+    partition(inner, rf, rb);
+    tl.end("MIMAINPART");
+    tl.begin("MOMAINPART");
+    if (withRids) {
+      const data::Tuple *t = outer->getData();
+      const uint64_t n = outer->getLocalSize();
+      sb.assign(F + 1, 0);
+      for (uint64_t i = 0; i < n; ++i) ++sb[(mix.apply(t[i].key) & (F - 1)) + 1];
+      for (uint32_t p = 0; p < F; ++p) sb[p + 1] += sb[p];
+      std::vector<uint64_t> cur(sb.begin(), sb.end() - 1);
+      sw.resize(n);
+      for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t k = mix.apply(t[i].key);
+        sw[cur[k & (F - 1)]++] = ((k >> nb) << plan.keyShift) | t[i].rid;
+      }
+    } else {
+      partition(outer, sf, sb);
+    }
+    tl.end("MOMAINPART");
+    utils::faultPoint("local");
+    utils::faultPoint("build_probe");
+    tl.begin("BPTASKTIME");
+    host::BitmapSemiResult res;
+    uint64_t *out = nullptr;
+    if (withRids) {
+      out = ctx->workspace().getArray<uint64_t>(outer->getLocalSize() + 1);
+      res = host::bitmapSemiRids(rf.data(), rb.data(), sw.data(), sb.data(), F, plan.keyShift, plan.bitmapBits,
+                                 plan.kind == core::JoinKind::Anti, out);
+    } else {
+      res = host::bitmapSemiCount(rf.data(), rb.data(), sf.data(), sb.data(), F, plan.bitmapBits);
+    }
+    tl.end("BPTASKTIME");
+    Outcome o;
+    if (!(res.flags & kernels::BM_FLAG_DUP)) {
+      finishSet(o, res.hits, res.misses);
+      if (withRids) {
+        JOIN_ASSERT(res.written == o.localMatches, "BitmapJoin", "set bitmap join wrote %lu rids for %lu tuples",
+                    (unsigned long)res.written, (unsigned long)o.localMatches);
+        o.rids = out;
+      }
+    }
+    agree(o, res.flags);
+    return o;
+  }
   utils::faultPoint("network");
   tl.begin("MIMAINPART");
   partition(inner, rf, rb);

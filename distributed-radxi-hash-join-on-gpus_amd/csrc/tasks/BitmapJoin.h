@@ -33,6 +33,14 @@
 //             redoes the join on the two-level pass
 // The host path (CPU, tests) runs the same plan with exact partitioning.
 //
+// Set mode (JoinPlan::bitmapSet, N = 1): semi / anti joins.  The inner side is
+// a set, so repeated inner keys are no error and only a fragment beyond the
+// planned range falls back.  Count-only: both sides as above, then
+// kernels::bitmapSemiCount (hits / misses per outer tuple; partition-group
+// passes work too).  Materializing: the outer side is scattered as 8-byte
+// CompressedTuples (kernels::netScatter into the same sampled layout) and
+// kernels::bitmapSemiRids writes the qualifying outer rids itself.
+//
 // Capacity spill (N = 1, JoinPlan::groupBudget): when both sides' fragment
 // windows exceed the memory budget, the sampled totals are read back once and
 // the network partitions cut into groups whose windows fit it; each group is
@@ -67,6 +75,11 @@ class BitmapJoin {
     uint64_t enqueueUs = 0;    // host clock when the last kernel of the join was enqueued
     double hostWaitMs = 0;     // host wait from there to the result (mailbox spin + stream sync)
     uint32_t groupPasses = 0;  // partition-group passes (JoinPlan::groupBudget), 0 = one pass
+    // Set mode: outer tuples with / without an inner partner (localMatches is
+    // the kind's count) and, materializing, the qualifying outer rids
+    // (workspace memory, localMatches of them).
+    uint64_t hits = 0, misses = 0;
+    const uint64_t *rids = nullptr;
   };
 
   // ev: 5 timing events of the caller (ev[0] already recorded at join start).
@@ -82,6 +95,7 @@ class BitmapJoin {
     uint32_t *frags = nullptr;
     kernels::BitmapSlices slices;
     uint64_t cap = 0;  // fragment capacity of all slices
+    uint32_t elemBytes = 4;  // 8: CompressedTuples with rids (the outer side of a materializing set join)
   };
   // narrowOk: 4-byte claim cursors are allowed (both sides of a fused bitmap
   // join must use the same cursor width; sideNarrow() says what one side needs).
@@ -91,10 +105,12 @@ class BitmapJoin {
     kernels::SampleScale sc{};
     uint64_t cap = 0;
   };
-  const SidePlan &sidePlan(uint64_t n, bool exact, uint32_t stride) const;
+  const SidePlan &sidePlan(uint64_t n, bool exact, uint32_t stride, uint32_t elemBytes = 4) const;
   void layoutSides(Side *sides, uint32_t count, bool exact, bool narrowOk);
   void scatterSide(Side &s);
-  bool sideNarrow(data::Relation *r, bool exact) const;
+  bool sideNarrow(data::Relation *r, bool exact, uint32_t elemBytes = 4) const;
+  // Set mode: the kind's count from hits / misses (checked against |S|).
+  void finishSet(Outcome &o, uint64_t hits, uint64_t misses) const;
   Outcome runDevice(bool exact);
   // Capacity spill (JoinPlan::groupBudget, N = 1): the network partitions in
   // groups whose fragment windows fit the budget, one pass per group.
