@@ -255,8 +255,16 @@ py::dict opBuildProbe(const at::Tensor &R, const at::Tensor &S, const at::Tensor
 // marks: bool per outer position; semi_count; semi_rids / anti_rids: the outer
 // rids the compaction emits for either kind (kernels/semi_join.hip and the
 // host twins).
-py::dict opBuildProbeMarks(const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR, const at::Tensor &partS,
-                           int64_t fragShift, int64_t keyShift, bool wide, int64_t rChunk, int64_t sChunk) {
+// With payload rows (build_probe_mark_rows): semi_rows / anti_rows instead of
+// the rid lists, each the whole [capacity + 64, 5] buffer the row-writing place
+// pass (kernels::markPlaceRows / host::markCompactRows) was given `capacity`
+// rows of: {rid, outerRows[rid - ridOffset]} per selected tuple below the
+// capacity, `sentinel` words everywhere else (the 64 guard rows included).
+constexpr int64_t kRowGuard = 64;
+constexpr int64_t kRowSentinel = 0x5A5A5A5A5A5A5A5All;
+py::dict buildProbeMarksImpl(const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR, const at::Tensor &partS,
+                             int64_t fragShift, int64_t keyShift, bool wide, int64_t rChunk, int64_t sChunk,
+                             const at::Tensor *outerRows, uint64_t ridOffset, int64_t outCapacity) {
   TORCH_CHECK(R.device() == S.device(), "R and S must live on the same device");
   TORCH_CHECK(rChunk >= 1 && sChunk >= 1, "r_chunk and s_chunk must be positive");
   setDevice(R);
@@ -276,7 +284,27 @@ py::dict opBuildProbeMarks(const at::Tensor &R, const at::Tensor &S, const at::T
   const int64_t n = S.size(0);
   const int64_t words = (int64_t)kernels::markWords((uint64_t)n);
   at::Tensor marks = at::zeros({words}, like(R));
-  at::Tensor rids[2] = {at::empty({n + 1}, like(R)), at::empty({n + 1}, like(R))};
+  const bool withRows = outerRows != nullptr;
+  const int64_t rowCap = outCapacity > 0 ? outCapacity : n;
+  at::Tensor rids[2], rowsOut[2];
+  for (int k = 0; k < 2; ++k) {
+    if (withRows)
+      rowsOut[k] = at::full({rowCap + kRowGuard, (int64_t)kernels::RID_ROW_WORDS}, kRowSentinel, like(R));
+    else
+      rids[k] = at::empty({n + 1}, like(R));
+  }
+  if (withRows) {
+    TORCH_CHECK(outerRows->device() == S.device() && outerRows->dim() == 2 &&
+                    outerRows->size(1) == (int64_t)kernels::ROW_WORDS && outerRows->is_contiguous() &&
+                    outerRows->scalar_type() == at::kLong,
+                "build_probe_mark_rows: outer_rows must be contiguous [n, 4] int64 on the relations' device");
+    if (n > 0) {  // every rid indexes a row
+      at::Tensor rid = wide ? S.select(1, 1) : at::bitwise_and(S, keyShift >= 64 ? (int64_t)-1 : ((int64_t)1 << keyShift) - 1);
+      TORCH_CHECK(rid.min().item<int64_t>() >= (int64_t)ridOffset &&
+                      rid.max().item<int64_t>() - (int64_t)ridOffset < outerRows->size(0),
+                  "build_probe_mark_rows: outer_rows do not cover the outer rids");
+    }
+  }
   uint64_t count[2] = {0, 0};
   if (R.is_cuda()) {
     at::Tensor ctr = at::zeros({4}, like(R));
@@ -317,9 +345,15 @@ py::dict opBuildProbeMarks(const at::Tensor &R, const at::Tensor &S, const at::T
                          ptr<uint32_t>(unitCounts), nullptr);
       kernels::scanExclusiveU32to64(ptr<uint32_t>(unitCounts), ptr<unsigned long long>(unitOffsets), unitCap,
                                     a.outCursor, scanWs.data_ptr(), nullptr);
-      kernels::markPlace(a, ptr<kernels::MarkUnit>(units), nUnits, unitCap, ptr<unsigned long long>(marks), anti != 0,
-                         ptr<unsigned long long>(unitOffsets), ptr<unsigned long long>(rids[anti]), (uint64_t)n,
-                         nullptr);
+      if (withRows)
+        kernels::markPlaceRows(a, ptr<kernels::MarkUnit>(units), nUnits, unitCap, ptr<unsigned long long>(marks),
+                               anti != 0, ptr<unsigned long long>(unitOffsets), nullptr, nullptr,
+                               kernels::KindRowShape::Rid, ptr<uint64_t>(*outerRows), ridOffset,
+                               ptr<uint64_t>(rowsOut[anti]), (uint64_t)rowCap, nullptr);
+      else
+        kernels::markPlace(a, ptr<kernels::MarkUnit>(units), nUnits, unitCap, ptr<unsigned long long>(marks), anti != 0,
+                           ptr<unsigned long long>(unitOffsets), ptr<unsigned long long>(rids[anti]), (uint64_t)n,
+                           nullptr);
       HIP_CHECK(hipDeviceSynchronize());
       at::Tensor h = ctr.cpu();
       count[anti] = (uint64_t)h[0].item<int64_t>();
@@ -327,8 +361,16 @@ py::dict opBuildProbeMarks(const at::Tensor &R, const at::Tensor &S, const at::T
     }
   } else {
     host::buildProbeMark(a, ptr<uint64_t>(marks));
-    for (int anti = 0; anti < 2; ++anti)
-      count[anti] = host::markCompact(a, ptr<uint64_t>(marks), anti != 0, ptr<uint64_t>(rids[anti]), (uint64_t)n);
+    for (int anti = 0; anti < 2; ++anti) {
+      if (withRows) {
+        uint64_t cursor = 0;
+        count[anti] = host::markCompactRows(a, ptr<uint64_t>(marks), anti != 0, kernels::KindRowShape::Rid,
+                                            ptr<uint64_t>(*outerRows), ridOffset, ptr<uint64_t>(rowsOut[anti]), &cursor,
+                                            (uint64_t)rowCap);
+      } else {
+        count[anti] = host::markCompact(a, ptr<uint64_t>(marks), anti != 0, ptr<uint64_t>(rids[anti]), (uint64_t)n);
+      }
+    }
   }
   at::Tensor pos = at::arange(n, like(R));
   at::Tensor bits = at::bitwise_and(
@@ -337,9 +379,86 @@ py::dict opBuildProbeMarks(const at::Tensor &R, const at::Tensor &S, const at::T
   d["marks"] = bits.to(at::kBool);
   d["semi_count"] = count[0];
   d["anti_count"] = count[1];
+  if (withRows) {
+    d["semi_rows"] = rowsOut[0];
+    d["anti_rows"] = rowsOut[1];
+    d["capacity"] = rowCap;
+    d["guard_rows"] = kRowGuard;
+    d["sentinel"] = kRowSentinel;
+    return d;
+  }
   d["semi_rids"] = rids[0].narrow(0, 0, (int64_t)count[0]);
   d["anti_rids"] = rids[1].narrow(0, 0, (int64_t)count[1]);
   return d;
+}
+
+py::dict opBuildProbeMarks(const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR, const at::Tensor &partS,
+                           int64_t fragShift, int64_t keyShift, bool wide, int64_t rChunk, int64_t sChunk) {
+  return buildProbeMarksImpl(R, S, partR, partS, fragShift, keyShift, wide, rChunk, sChunk, nullptr, 0, 0);
+}
+
+py::dict opBuildProbeMarkRows(const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR,
+                              const at::Tensor &partS, int64_t fragShift, int64_t keyShift, bool wide, int64_t rChunk,
+                              int64_t sChunk, const at::Tensor &outerRows, uint64_t ridOffset, int64_t outCapacity) {
+  TORCH_CHECK(outCapacity >= 0, "build_probe_mark_rows: out_capacity must not be negative (0 = the outer side)");
+  return buildProbeMarksImpl(R, S, partR, partS, fragShift, keyShift, wide, rChunk, sChunk, &outerRows, ridOffset,
+                             outCapacity);
+}
+
+// ---- payload rows over rid / pair lists (kernels/kind_rows.hip, materialize.hip; host twins)
+static void checkRowsTensor(const at::Tensor &rows, const at::Tensor &like, const char *what) {
+  TORCH_CHECK(rows.device() == like.device() && rows.dim() == 2 && rows.size(1) == (int64_t)kernels::ROW_WORDS &&
+                  rows.is_contiguous() && rows.scalar_type() == at::kLong,
+              what, ": payload rows must be contiguous [n, 4] int64 on the list's device");
+}
+
+// Every rid but NULL_RID indexes a row of its column.
+static void checkRidsCovered(const at::Tensor &rids, const at::Tensor &rows, uint64_t off, const char *what) {
+  at::Tensor real = rids.masked_select(rids.ne((int64_t)kernels::NULL_RID));
+  if (real.numel() == 0) return;
+  TORCH_CHECK(real.min().item<int64_t>() >= (int64_t)off && real.max().item<int64_t>() - (int64_t)off < rows.size(0),
+              what, ": the payload rows do not cover the rids");
+}
+
+at::Tensor opRidRows(const at::Tensor &rids, const at::Tensor &rows, uint64_t ridOffset) {
+  TORCH_CHECK(rids.dim() == 1 && rids.scalar_type() == at::kLong && rids.is_contiguous(),
+              "rid_rows: rids must be contiguous int64 [n]");
+  checkRowsTensor(rows, rids, "rid_rows");
+  checkRidsCovered(rids, rows, ridOffset, "rid_rows");
+  setDevice(rids);
+  at::Tensor out = at::empty({rids.size(0), (int64_t)kernels::RID_ROW_WORDS}, like(rids));
+  if (rids.is_cuda()) {
+    kernels::ridRows(ptr<uint64_t>(rids), (uint64_t)rids.size(0), ptr<uint64_t>(rows), ridOffset, ptr<uint64_t>(out),
+                     nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+  } else {
+    host::ridRows(ptr<uint64_t>(rids), (uint64_t)rids.size(0), ptr<uint64_t>(rows), ridOffset, ptr<uint64_t>(out));
+  }
+  return out;
+}
+
+at::Tensor opPairRows(const at::Tensor &pairs, const at::Tensor &rowsA, uint64_t offA, const at::Tensor &rowsB,
+                      uint64_t offB, int64_t variant) {
+  TORCH_CHECK(pairs.dim() == 2 && pairs.size(1) == 2 && pairs.scalar_type() == at::kLong && pairs.is_contiguous(),
+              "pair_rows: pairs must be contiguous int64 [n, 2]");
+  TORCH_CHECK(variant >= 0 && variant <= 3, "pair_rows: variant 0-3");
+  checkRowsTensor(rowsA, pairs, "pair_rows");
+  checkRowsTensor(rowsB, pairs, "pair_rows");
+  if (pairs.size(0) > 0) {
+    checkRidsCovered(pairs.select(1, 0), rowsA, offA, "pair_rows (inner)");
+    checkRidsCovered(pairs.select(1, 1), rowsB, offB, "pair_rows (outer)");
+  }
+  setDevice(pairs);
+  at::Tensor out = at::empty({pairs.size(0), (int64_t)kernels::PAIR_ROW_WORDS}, like(pairs));
+  if (pairs.is_cuda()) {
+    kernels::materializeLocal(ptr<ulonglong2>(pairs), (uint64_t)pairs.size(0), ptr<uint64_t>(rowsA), offA,
+                              ptr<uint64_t>(rowsB), offB, ptr<uint64_t>(out), nullptr, (uint32_t)variant, true);
+    HIP_CHECK(hipDeviceSynchronize());
+  } else {
+    host::pairRows(ptr<ulonglong2>(pairs), (uint64_t)pairs.size(0), ptr<uint64_t>(rowsA), offA, ptr<uint64_t>(rowsB),
+                   offB, ptr<uint64_t>(out));
+  }
+  return out;
 }
 
 // ---- outer join over partition-major inputs: count + marks, place, pad -----
@@ -348,9 +467,18 @@ py::dict opBuildProbeMarks(const at::Tensor &R, const at::Tensor &S, const at::T
 // unmatched outer ones (keep_outer); inner_marks / outer_marks: bool per
 // position of R / S (all false for a side that is not kept)
 // (kernels/outer_join.hip and the host twins).
-py::dict opBuildProbeOuter(const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR, const at::Tensor &partS,
-                           int64_t fragShift, int64_t keyShift, bool wide, int64_t rChunk, int64_t sChunk,
-                           bool keepInner, bool keepOuter) {
+// With payload rows (build_probe_outer_rows): also `rows`, the whole
+// [m + 64, 10] buffer: the matched pairs' rows (from the pair list: the fused
+// row kernels of the place pass need the split layout), then the padded rows of
+// the kept sides written by kernels::markPlaceRows / host::markCompactRows
+// from the same bases as the pairs; `sentinel` words in the 64 guard rows.
+struct OuterRowsArgs {
+  const at::Tensor *rowsR, *rowsS;
+  uint64_t offR, offS;
+};
+py::dict buildProbeOuterImpl(const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR, const at::Tensor &partS,
+                             int64_t fragShift, int64_t keyShift, bool wide, int64_t rChunk, int64_t sChunk,
+                             bool keepInner, bool keepOuter, const OuterRowsArgs *rowArgs) {
   TORCH_CHECK(R.device() == S.device(), "R and S must live on the same device");
   TORCH_CHECK(rChunk >= 1 && sChunk >= 1, "r_chunk and s_chunk must be positive");
   TORCH_CHECK(keepInner || keepOuter, "build_probe_outer: keep_inner or keep_outer (or both)");
@@ -375,7 +503,26 @@ py::dict opBuildProbeOuter(const at::Tensor &R, const at::Tensor &S, const at::T
   unsigned long long *mp[2] = {keepInner ? ptr<unsigned long long>(marks[0]) : nullptr,
                                keepOuter ? ptr<unsigned long long>(marks[1]) : nullptr};
   uint64_t matched = 0, unmatched[2] = {0, 0};
-  at::Tensor pairs;
+  at::Tensor pairs, rowsOut;
+  if (rowArgs) {
+    const at::Tensor *rel[2] = {&R, &S}, *rows[2] = {rowArgs->rowsR, rowArgs->rowsS};
+    const uint64_t off[2] = {rowArgs->offR, rowArgs->offS};
+    for (int r = 0; r < 2; ++r) {
+      TORCH_CHECK(rows[r]->device() == R.device() && rows[r]->dim() == 2 &&
+                      rows[r]->size(1) == (int64_t)kernels::ROW_WORDS && rows[r]->is_contiguous() &&
+                      rows[r]->scalar_type() == at::kLong,
+                  "build_probe_outer_rows: payload rows must be contiguous [n, 4] int64 on the relations' device");
+      if (n[r] == 0) continue;  // every rid indexes a row
+      at::Tensor rid = wide ? rel[r]->select(1, 1)
+                            : at::bitwise_and(*rel[r], keyShift >= 64 ? (int64_t)-1 : ((int64_t)1 << keyShift) - 1);
+      TORCH_CHECK(rid.min().item<int64_t>() >= (int64_t)off[r] &&
+                      rid.max().item<int64_t>() - (int64_t)off[r] < rows[r]->size(0),
+                  "build_probe_outer_rows: the payload rows do not cover the rids");
+    }
+  }
+  auto newRows = [&](uint64_t m) {
+    return at::full({(int64_t)m + kRowGuard, (int64_t)kernels::PAIR_ROW_WORDS}, kRowSentinel, like(R));
+  };
   if (R.is_cuda()) {
     at::Tensor ctr = at::zeros({8}, like(R));
     auto *c = reinterpret_cast<unsigned long long *>(ctr.data_ptr());
@@ -452,6 +599,19 @@ py::dict opBuildProbeOuter(const at::Tensor &R, const at::Tensor &S, const at::T
                                 rows, nullptr);
     HIP_CHECK(hipDeviceSynchronize());
     TORCH_CHECK((uint64_t)ctr.cpu()[3].item<int64_t>() == matched, "build_probe_outer: count and place passes disagree");
+    if (rowArgs) {
+      rowsOut = newRows(rows);
+      kernels::materializeLocal(a.outPairs, matched, ptr<uint64_t>(*rowArgs->rowsR), rowArgs->offR, ptr<uint64_t>(*rowArgs->rowsS),
+                                rowArgs->offS, ptr<uint64_t>(rowsOut), nullptr);
+      for (int r = 0; r < 2; ++r)
+        if (keep[r])
+          kernels::markPlaceRows(ua[r], ptr<kernels::MarkUnit>(units[r]), nUnits + r, unitCap[r], mp[r], true,
+                                 ptr<unsigned long long>(unitOffsets[r]), c + 1, r ? c + 4 : nullptr,
+                                 r ? kernels::KindRowShape::OuterPad : kernels::KindRowShape::InnerPad,
+                                 ptr<uint64_t>(r ? *rowArgs->rowsS : *rowArgs->rowsR), r ? rowArgs->offS : rowArgs->offR,
+                                 ptr<uint64_t>(rowsOut), rows, nullptr);
+      HIP_CHECK(hipDeviceSynchronize());
+    }
   } else {
     uint64_t cursor = 0, cap = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {  // first a counting walk, then the exactly sized one
@@ -470,8 +630,25 @@ py::dict opBuildProbeOuter(const at::Tensor &R, const at::Tensor &S, const at::T
                                : 0;
       cap = cursor;
     }
+    if (rowArgs) {
+      rowsOut = newRows(cap);
+      host::pairRows(a.outPairs, matched, ptr<uint64_t>(*rowArgs->rowsR), rowArgs->offR, ptr<uint64_t>(*rowArgs->rowsS), rowArgs->offS,
+                     ptr<uint64_t>(rowsOut));
+      uint64_t at = matched;
+      for (int r = 0; r < 2; ++r)
+        if (keep[r])
+          host::markCompactRows(a, reinterpret_cast<const uint64_t *>(mp[r]), true,
+                                r ? kernels::KindRowShape::OuterPad : kernels::KindRowShape::InnerPad,
+                                ptr<uint64_t>(r ? *rowArgs->rowsS : *rowArgs->rowsR), r ? rowArgs->offS : rowArgs->offR,
+                                ptr<uint64_t>(rowsOut), &at, cap);
+    }
   }
   py::dict d;
+  if (rowArgs) {
+    d["rows"] = rowsOut;
+    d["guard_rows"] = kRowGuard;
+    d["sentinel"] = kRowSentinel;
+  }
   const char *names[2] = {"inner_marks", "outer_marks"};
   for (int r = 0; r < 2; ++r) {
     at::Tensor pos = at::arange(n[r], like(R));
@@ -485,6 +662,21 @@ py::dict opBuildProbeOuter(const at::Tensor &R, const at::Tensor &S, const at::T
   d["unmatched_inner"] = unmatched[0];
   d["unmatched_outer"] = unmatched[1];
   return d;
+}
+
+py::dict opBuildProbeOuter(const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR, const at::Tensor &partS,
+                           int64_t fragShift, int64_t keyShift, bool wide, int64_t rChunk, int64_t sChunk,
+                           bool keepInner, bool keepOuter) {
+  return buildProbeOuterImpl(R, S, partR, partS, fragShift, keyShift, wide, rChunk, sChunk, keepInner, keepOuter,
+                             nullptr);
+}
+
+py::dict opBuildProbeOuterRows(const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR,
+                               const at::Tensor &partS, int64_t fragShift, int64_t keyShift, bool wide, int64_t rChunk,
+                               int64_t sChunk, bool keepInner, bool keepOuter, const at::Tensor &innerRows,
+                               uint64_t innerOffset, const at::Tensor &outerRows, uint64_t outerOffset) {
+  const OuterRowsArgs pr{&innerRows, &outerRows, innerOffset, outerOffset};
+  return buildProbeOuterImpl(R, S, partR, partS, fragShift, keyShift, wide, rChunk, sChunk, keepInner, keepOuter, &pr);
 }
 
 at::Tensor opGenerate(int64_t n, int64_t globalOffset, int64_t globalSize, const data::GenSpec &spec,
@@ -1117,6 +1309,66 @@ static void checkPayloadCover(const operators::HashJoin &j, const at::Tensor &a,
   }
 }
 
+// Payload rows of a kind != INNER join (join_rows / materialize_rows): refused
+// for N > 1 on every rank before anything is exchanged, then the shapes and,
+// from ridMin / ridMax, the payload cover -- for SEMI / ANTI of the outer side
+// only (the inner payload is never read: an empty [0, 4] tensor will do).
+static void checkKindRows(const operators::HashJoin &j, const char *entry, const at::Tensor &innerRows,
+                          uint64_t innerOffset, const at::Tensor &outerRows, uint64_t outerOffset) {
+  const core::JoinKind kind = j.getConfig().kind;
+  const uint32_t world = j.context()->comm()->size();
+  TORCH_CHECK(world == 1, entry, ": payload rows of a kind=", core::joinKindName(kind),
+              " join need a single rank, this join runs on ", world,
+              " (a NULL rid has no owner to fetch a row from; rid lists are not exchanged)");
+  TORCH_CHECK(innerRows.dim() == 2 && innerRows.size(1) == (int64_t)kernels::ROW_WORDS && outerRows.dim() == 2 &&
+                  outerRows.size(1) == (int64_t)kernels::ROW_WORDS && innerRows.scalar_type() == at::kLong &&
+                  outerRows.scalar_type() == at::kLong,
+              entry, ": payload rows must be [n, 4] int64 (32 bytes)");
+  TORCH_CHECK(innerRows.is_contiguous() && outerRows.is_contiguous(), entry, ": payload rows must be contiguous");
+  TORCH_CHECK(outerRows.is_cuda() == j.context()->onDevice() &&
+                  (core::isRidKind(kind) || innerRows.device() == outerRows.device()),
+              entry, ": payload rows must live where the join runs");
+  const uint64_t off[2] = {innerOffset, outerOffset}, rows[2] = {(uint64_t)innerRows.size(0), (uint64_t)outerRows.size(0)};
+  for (int r = core::isRidKind(kind) ? 1 : 0; r < 2; ++r) {
+    const uint64_t lo = j.ridMin(r), hi = j.ridMax(r);
+    TORCH_CHECK(lo > hi || (lo >= off[r] && hi - off[r] < rows[r]), entry, ": ", r ? "outer" : "inner",
+                " payload rows [", off[r], ", ", off[r] + rows[r], ") do not cover this rank's rids [", lo, ", ", hi, "]");
+  }
+}
+
+// The unfused rows of run `r`, from its rid list (SEMI / ANTI: ridRows) or its
+// NULL-padded pair list (outer kinds: the NULL-aware materializeLocal); host
+// joins through the host twins.
+static at::Tensor kindRowsUnfused(operators::HashJoin &j, const operators::JoinResult &r, const at::Tensor &innerRows,
+                                  uint64_t innerOffset, const at::Tensor &outerRows, uint64_t outerOffset) {
+  TORCH_CHECK(!r.rowsFused, "the last run wrote its rows directly (join_rows): it left no rid or pair list");
+  const bool ridKind = core::isRidKind(j.getConfig().kind), dev = j.context()->onDevice();
+  const uint64_t n = ridKind ? r.outputRids : r.outputPairs;
+  at::Tensor out = at::empty({(int64_t)n, (int64_t)(ridKind ? kernels::RID_ROW_WORDS : kernels::PAIR_ROW_WORDS)},
+                             at::TensorOptions().dtype(at::kLong).device(outerRows.device()));
+  if (!n) return out;
+  HJ_CHECK(ridKind ? j.outputRidsValid() : j.outputValid(),
+           "the rids / pairs of the last run were in the engine workspace, which a later join, plan or trim_workspace "
+           "on the same context has since reused; materialize the rows right after run()");
+  hipStream_t s = dev ? j.context()->stream() : nullptr;
+  py::gil_scoped_release nogil;
+  if (ridKind) {
+    if (dev)
+      kernels::ridRows(j.getOutputRids(), n, ptr<uint64_t>(outerRows), outerOffset, ptr<uint64_t>(out), s);
+    else
+      host::ridRows(j.getOutputRids(), n, ptr<uint64_t>(outerRows), outerOffset, ptr<uint64_t>(out));
+  } else {
+    if (dev)
+      kernels::materializeLocal(j.getOutput(), n, ptr<uint64_t>(innerRows), innerOffset, ptr<uint64_t>(outerRows),
+                                outerOffset, ptr<uint64_t>(out), s, j.getConfig().variants.matVariant, true);
+    else
+      host::pairRows(j.getOutput(), n, ptr<uint64_t>(innerRows), innerOffset, ptr<uint64_t>(outerRows), outerOffset,
+                     ptr<uint64_t>(out));
+  }
+  if (dev) HIP_CHECK(hipStreamSynchronize(s));
+  return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "MI355X-native distributed radix hash join engine (native core)";
   m.attr("ARCH") = "gfx950";
@@ -1229,6 +1481,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                     [](core::JoinConfig &c, uint32_t v) { c.variants.rowsLds = v; })
       .def_property("mat_variant", [](const core::JoinConfig &c) { return c.variants.matVariant; },
                     [](core::JoinConfig &c, uint32_t v) { c.variants.matVariant = v; })
+      .def_property("kind_rows", [](const core::JoinConfig &c) { return c.variants.kindRows; },
+                    [](core::JoinConfig &c, uint32_t v) { c.variants.kindRows = v; })
       .def("__repr__", &core::JoinConfig::describe);
 
   py::class_<core::JoinPlan>(m, "JoinPlan")
@@ -1685,6 +1939,86 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           },
           py::arg("context"), py::arg("inner_rows"), py::arg("inner_rid_offset"), py::arg("inner_global_rows"),
           py::arg("outer_rows"), py::arg("outer_rid_offset"), py::arg("outer_global_rows"))
+      .def_property_readonly("can_fuse_kind_rows", &operators::HashJoin::canFuseKindRows)
+      .def(
+          "join_rows",
+          [](py::object self, std::shared_ptr<core::ExecContext> ctx, at::Tensor innerRows, uint64_t innerOffset,
+             uint64_t innerGlobal, at::Tensor outerRows, uint64_t outerOffset, uint64_t outerGlobal) -> py::object {
+            // One join + payload rows for any kind: (result dict, rows).
+            // INNER: join_materialized.  SEMI / ANTI: [m, 5] {outer rid, outer
+            // row}; outer kinds: [m, 10] inner-join rows, a missing side all
+            // NULL_RID.  N = 1 for kind != INNER.
+            auto &j = self.cast<operators::HashJoin &>();
+            TORCH_CHECK(j.getConfig().materialize, "join_rows needs materialize=True");
+            if (j.getConfig().kind == core::JoinKind::Inner)
+              return self.attr("join_materialized")(ctx, innerRows, innerOffset, innerGlobal, outerRows, outerOffset,
+                                                    outerGlobal);
+            checkKindRows(j, "join_rows", innerRows, innerOffset, outerRows, outerOffset);
+            const core::JoinKind kind = j.getConfig().kind;
+            const bool ridKind = core::isRidKind(kind), dev = outerRows.is_cuda();
+            const int64_t W = ridKind ? kernels::RID_ROW_WORDS : kernels::PAIR_ROW_WORDS;
+            const auto opts = at::TensorOptions().dtype(at::kLong).device(outerRows.device());
+            operators::JoinResult r;
+            if (dev) HIP_CHECK(hipDeviceSynchronize());  // payloads written on other streams
+            if (dev && j.canFuseKindRows()) {
+              struct Clear {
+                operators::HashJoin &j;
+                ~Clear() { j.clearRowSink(); }
+              } clear{j};
+              // Semi / anti: at most one row per outer tuple.  Outer kinds: the
+              // unmatched rows never exceed the default, the pairs can.
+              uint64_t cap = ridKind ? std::max<uint64_t>(1, (uint64_t)outerRows.size(0))
+                             : j.getConfig().outputCapacity
+                                 ? j.getConfig().outputCapacity
+                                 : (uint64_t)outerRows.size(0) + 1024 +
+                                       (core::preservesInner(kind) ? (uint64_t)innerRows.size(0) : 0);
+              for (int attempt = 0; attempt < 2; ++attempt) {
+                at::Tensor out = at::empty({(int64_t)cap, W}, opts);
+                kernels::RowSink sk;
+                sk.rowsA = ridKind ? nullptr : ptr<uint64_t>(innerRows);
+                sk.offA = innerOffset;
+                sk.rowsAN = (uint64_t)innerRows.size(0);
+                sk.rowsB = ptr<uint64_t>(outerRows);
+                sk.offB = outerOffset;
+                sk.rowsBN = (uint64_t)outerRows.size(0);
+                sk.out = ptr<uint64_t>(out);
+                sk.capacity = cap;
+                j.setKindRowSink(sk);
+                {
+                  py::gil_scoped_release nogil;
+                  r = j.run();
+                }
+                if (!r.rowsFused) break;  // this run took another plan: rows from its rid / pair list below
+                const uint64_t n = ridKind ? r.outputRids : r.outputPairs;
+                if (!r.outputOverflow) return py::make_tuple(resultToDict(r), out.narrow(0, 0, (int64_t)n));
+                cap = n;  // more rows than the first guess: once more, exactly sized
+              }
+              TORCH_CHECK(!r.rowsFused, "join_rows: row output overflowed twice");
+            } else {
+              py::gil_scoped_release nogil;
+              r = j.run();
+            }
+            at::Tensor out = kindRowsUnfused(j, r, innerRows, innerOffset, outerRows, outerOffset);
+            return py::make_tuple(resultToDict(r), out);
+          },
+          py::arg("context"), py::arg("inner_rows"), py::arg("inner_rid_offset"), py::arg("inner_global_rows"),
+          py::arg("outer_rows"), py::arg("outer_rid_offset"), py::arg("outer_global_rows"))
+      .def(
+          "materialize_rows",
+          [](py::object self, std::shared_ptr<core::ExecContext> ctx, at::Tensor innerRows, uint64_t innerOffset,
+             uint64_t innerGlobal, at::Tensor outerRows, uint64_t outerOffset, uint64_t outerGlobal) -> py::object {
+            // Payload rows of the last run(), from its rid / pair list (join_rows' formats).
+            auto &j = self.cast<operators::HashJoin &>();
+            TORCH_CHECK(j.getConfig().materialize, "materialize_rows: the join was not run with materialize=True");
+            if (j.getConfig().kind == core::JoinKind::Inner)
+              return self.attr("materialize_payloads")(ctx, innerRows, innerOffset, innerGlobal, outerRows, outerOffset,
+                                                       outerGlobal);
+            checkKindRows(j, "materialize_rows", innerRows, innerOffset, outerRows, outerOffset);
+            if (outerRows.is_cuda()) HIP_CHECK(hipDeviceSynchronize());
+            return py::cast(kindRowsUnfused(j, j.lastResult(), innerRows, innerOffset, outerRows, outerOffset));
+          },
+          py::arg("context"), py::arg("inner_rows"), py::arg("inner_rid_offset"), py::arg("inner_global_rows"),
+          py::arg("outer_rows"), py::arg("outer_rid_offset"), py::arg("outer_global_rows"))
       .def("output", [](operators::HashJoin &j) {
         const auto &r = j.lastResult();
         const uint64_t n = r.outputPairs;
@@ -1868,6 +2202,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   ops.def("build_probe_marks", &opBuildProbeMarks, py::arg("R"), py::arg("S"), py::arg("part_r"), py::arg("part_s"),
           py::arg("frag_shift"), py::arg("key_shift"), py::arg("wide") = false, py::arg("r_chunk") = 4096,
           py::arg("s_chunk") = 65536);
+  ops.def("build_probe_mark_rows", &opBuildProbeMarkRows, py::arg("R"), py::arg("S"), py::arg("part_r"),
+          py::arg("part_s"), py::arg("frag_shift"), py::arg("key_shift"), py::arg("wide"), py::arg("r_chunk"),
+          py::arg("s_chunk"), py::arg("outer_rows"), py::arg("rid_offset"), py::arg("out_capacity") = 0);
+  ops.def("build_probe_outer_rows", &opBuildProbeOuterRows, py::arg("R"), py::arg("S"), py::arg("part_r"),
+          py::arg("part_s"), py::arg("frag_shift"), py::arg("key_shift"), py::arg("wide"), py::arg("r_chunk"),
+          py::arg("s_chunk"), py::arg("keep_inner"), py::arg("keep_outer"), py::arg("inner_rows"),
+          py::arg("inner_rid_offset"), py::arg("outer_rows"), py::arg("outer_rid_offset"));
+  ops.def("rid_rows", &opRidRows, py::arg("rids"), py::arg("rows"), py::arg("rid_offset"));
+  ops.def("pair_rows", &opPairRows, py::arg("pairs"), py::arg("rows_a"), py::arg("off_a"), py::arg("rows_b"),
+          py::arg("off_b"), py::arg("variant") = 1);
   ops.def("build_probe_outer", &opBuildProbeOuter, py::arg("R"), py::arg("S"), py::arg("part_r"), py::arg("part_s"),
           py::arg("frag_shift"), py::arg("key_shift"), py::arg("wide") = false, py::arg("r_chunk") = 4096,
           py::arg("s_chunk") = 65536, py::arg("keep_inner") = true, py::arg("keep_outer") = true);

@@ -102,7 +102,8 @@ struct JoinConfig {
   // (HashJoin::getOutputRids) instead of pairs.  Outer kinds: with materialize
   // the output is the NULL-padded pair list (HashJoin::getOutput); refused when
   // a rid equals NULL_RID.  No kind but Inner is combined with outputHost, a
-  // RowSink, or a materializing capacity spill.
+  // RowSink (HashJoin::setRowSink; their payload rows go through
+  // setKindRowSink at N = 1), or a materializing capacity spill.
   JoinKind kind = JoinKind::Inner;
   uint32_t networkBits = 0;   // radix bits of the network pass (0 = auto)
   uint32_t localBits = 0;     // radix bits of the local pass (0 = auto; ignored if !twoLevel)

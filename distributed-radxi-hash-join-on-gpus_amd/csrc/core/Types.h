@@ -51,6 +51,11 @@ struct KernelVariants {
                               // keys), 7 = the v2 bucket table (bpKeySpanKernel) everywhere
   uint32_t rowsLds = 1;       // fused row output with the inner rows cached in LDS (0 = staged kernel)
   uint32_t matVariant = 1;    // late-materialization store/load flavour (materialize.hip)
+  uint32_t kindRows = 2;      // payload rows of semi / anti / outer joins (HashJoin::canFuseKindRows): 1 = written by
+                              // the place pass where the plan allows it (markPlaceRows), 0 = always from the rid /
+                              // pair list by the unfused kernels (ridRows, NULL-aware materializeLocal), 2 = the
+                              // measured faster per kind family: semi / anti fused, outer kinds unfused
+                              // (kernels/kind_rows.hip, profiles/kind_rows/README.md)
 };
 
 }  // namespace hpcjoin

@@ -348,6 +348,71 @@ uint64_t markCompactPairs(const kernels::BPArgs &a, const uint64_t *marks, bool 
   return n;
 }
 
+uint64_t markCompactRows(const kernels::BPArgs &a, const uint64_t *marks, bool anti, kernels::KindRowShape shape,
+                         const uint64_t *rows, uint64_t rowOffset, uint64_t *out, uint64_t *cursor,
+                         uint64_t outCapacity) {
+  using kernels::KindRowShape;
+  using kernels::NULL_RID;
+  const uint64_t ridMask = a.keyShift >= 64 ? ~0ull : ((1ull << a.keyShift) - 1);
+  const bool innerSide = shape == KindRowShape::InnerPad;
+  const void *base = innerSide ? a.R : a.S;
+  const uint64_t *pb = innerSide ? a.partR : a.partS, *pe = innerSide ? a.partREnd : a.partSEnd;
+  const uint32_t W = kernels::kindRowWords(shape);
+  uint64_t n = 0;
+  for (uint32_t p = 0; p < a.P; ++p) {
+    const uint64_t b = pb[p], e = pe ? pe[p] : pb[p + 1];
+    for (uint64_t i = b; i < e; ++i) {
+      const bool marked = (marks[i >> 6] >> (i & 63)) & 1;
+      if (marked == anti) continue;
+      const uint64_t rid =
+          a.wide ? static_cast<const data::Tuple *>(base)[i].rid : (static_cast<const uint64_t *>(base)[i] & ridMask);
+      const uint64_t at = (*cursor)++;
+      ++n;
+      if (!out || at >= outCapacity) continue;
+      uint64_t *o = out + at * W;
+      const uint64_t *row = rows + (rid - rowOffset) * kernels::ROW_WORDS;
+      if (shape == KindRowShape::Rid) {
+        o[0] = rid;
+        std::copy(row, row + kernels::ROW_WORDS, o + 1);
+      } else {
+        o[0] = innerSide ? rid : NULL_RID;
+        o[1] = innerSide ? NULL_RID : rid;
+        std::copy(row, row + kernels::ROW_WORDS, o + (innerSide ? 2 : 6));
+        std::fill(o + (innerSide ? 6 : 2), o + (innerSide ? 10 : 6), (uint64_t)NULL_RID);
+      }
+    }
+  }
+  return n;
+}
+
+void ridRows(const uint64_t *rids, uint64_t n, const uint64_t *rows, uint64_t rowOffset, uint64_t *out) {
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t *row = rows + (rids[i] - rowOffset) * kernels::ROW_WORDS;
+    out[i * kernels::RID_ROW_WORDS] = rids[i];
+    std::copy(row, row + kernels::ROW_WORDS, out + i * kernels::RID_ROW_WORDS + 1);
+  }
+}
+
+void pairRows(const ulonglong2 *pairs, uint64_t n, const uint64_t *rowsA, uint64_t offA, const uint64_t *rowsB,
+              uint64_t offB, uint64_t *out) {
+  for (uint64_t i = 0; i < n; ++i) {
+    uint64_t *o = out + i * kernels::PAIR_ROW_WORDS;
+    o[0] = pairs[i].x;
+    o[1] = pairs[i].y;
+    const uint64_t rid[2] = {pairs[i].x, pairs[i].y}, off[2] = {offA, offB};
+    const uint64_t *cols[2] = {rowsA, rowsB};
+    for (int s = 0; s < 2; ++s) {
+      uint64_t *dst = o + 2 + s * kernels::ROW_WORDS;
+      if (rid[s] == kernels::NULL_RID) {
+        std::fill(dst, dst + kernels::ROW_WORDS, (uint64_t)kernels::NULL_RID);
+      } else {
+        const uint64_t *row = cols[s] + (rid[s] - off[s]) * kernels::ROW_WORDS;
+        std::copy(row, row + kernels::ROW_WORDS, dst);
+      }
+    }
+  }
+}
+
 // One partition's set bitmap over the whole planned range (the device kernels
 // split 21-bit ranges over two workgroups; the host needs no pieces).
 namespace {

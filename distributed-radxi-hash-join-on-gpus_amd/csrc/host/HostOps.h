@@ -60,6 +60,20 @@ uint64_t buildProbeOuter(const kernels::BPArgs &a, uint64_t *marksR, uint64_t *m
 uint64_t markCompactPairs(const kernels::BPArgs &a, const uint64_t *marks, bool innerSide, ulonglong2 *out,
                           uint64_t *cursor, uint64_t outCapacity);
 
+// Payload rows of semi, anti and outer joins (twins of kernels/kind_rows.hip;
+// row shapes: kernels::KindRowShape).  markCompactRows appends one row per
+// marked (anti: unmarked) position of the partitions of a.S (InnerPad: of a.R)
+// from out row *cursor, as markCompactPairs does; ridRows writes
+// out[i] = {rids[i], rows[rids[i] - rowOffset]}; pairRows writes the 10-word
+// row of every pair, a NULL_RID side as five NULL_RID words (no row is read
+// for it).
+uint64_t markCompactRows(const kernels::BPArgs &a, const uint64_t *marks, bool anti, kernels::KindRowShape shape,
+                         const uint64_t *rows, uint64_t rowOffset, uint64_t *out, uint64_t *cursor,
+                         uint64_t outCapacity);
+void ridRows(const uint64_t *rids, uint64_t n, const uint64_t *rows, uint64_t rowOffset, uint64_t *out);
+void pairRows(const ulonglong2 *pairs, uint64_t n, const uint64_t *rowsA, uint64_t offA, const uint64_t *rowsB,
+              uint64_t offB, uint64_t *out);
+
 // Set-semantics bitmap join (twins of kernels::bitmapSemiCount / bitmapSemiRids)
 // over exactly partitioned sides: partition p holds elements [begin[p],
 // begin[p + 1]).  Inner: u32 fragments; outer: u32 fragments (count) or 8-byte

@@ -865,10 +865,34 @@ void gatherRows(const uint64_t *rids, uint64_t n, uint64_t ridOffset, const uint
                 hipStream_t s);
 // out[idx[j] * stride + col .. + ROW_WORDS) = rows[j]
 // Single rank: out[i] = {pair, rowsA[pair.x - offA], rowsB[pair.y - offB]} (10 words).
+// nulls: either rid of a pair may be NULL_RID (outer-join rows); that side's
+// four payload words come out as NULL_RID and no row is loaded for it.
 void materializeLocal(const ulonglong2 *pairs, uint64_t n, const uint64_t *rowsA, uint64_t offA,
-                      const uint64_t *rowsB, uint64_t offB, uint64_t *out, hipStream_t s, uint32_t variant = 1);
+                      const uint64_t *rowsB, uint64_t offB, uint64_t *out, hipStream_t s, uint32_t variant = 1,
+                      bool nulls = false);
 void placeRows(const uint64_t *rows, const uint64_t *idx, uint64_t n, uint64_t *out, uint32_t strideWords,
                uint32_t colWord, hipStream_t s);
+
+// Payload rows of semi, anti and outer joins (kind_rows.hip), N = 1.
+//   Rid       5 words  {rid, row}                       semi / anti result row
+//   InnerPad 10 words  {rid, NULL_RID, row, NULL x 4}    unmatched inner tuple of an outer join
+//   OuterPad 10 words  {NULL_RID, rid, NULL x 4, row}    unmatched outer tuple
+enum class KindRowShape : uint32_t { Rid = 0, InnerPad = 1, OuterPad = 2 };
+constexpr uint32_t RID_ROW_WORDS = 1 + ROW_WORDS;
+constexpr uint32_t PAIR_ROW_WORDS = 2 + 2 * ROW_WORDS;
+HJ_HD uint32_t kindRowWords(KindRowShape s) { return s == KindRowShape::Rid ? RID_ROW_WORDS : PAIR_ROW_WORDS; }
+// The row-writing twin of markPlace / markPlacePairs over the units of a.S:
+// one row of `shape` per marked (anti: unmarked) tuple, its payload
+// rows[rid - rowOffset], at out row *base0 + *base1 + unitOffsets[u] ... in
+// position order (either base may be null; rows at or beyond outCapacity are
+// not stored).
+void markPlaceRows(const BPArgs &a, const MarkUnit *units, const uint32_t *nUnits, uint32_t capacity,
+                   const unsigned long long *marks, bool anti, const unsigned long long *unitOffsets,
+                   const unsigned long long *base0, const unsigned long long *base1, KindRowShape shape,
+                   const uint64_t *rows, uint64_t rowOffset, uint64_t *out, uint64_t outCapacity, hipStream_t s);
+// out[i] = {rids[i], rows[rids[i] - rowOffset]} (5 words).
+void ridRows(const uint64_t *rids, uint64_t n, const uint64_t *rows, uint64_t rowOffset, uint64_t *out,
+             hipStream_t s);
 // Every HIP source file is its own code object, loaded by the runtime at the
 // first use of one of its kernels -- 1-2 ms each, which landed inside the
 // first join.  ExecContext calls this once per process and device: one
@@ -885,6 +909,7 @@ void preloadScan();
 void preloadWire();
 void preloadCollectives();
 void preloadMaterialize();
+void preloadKindRows();
 void preloadDatagen();
 inline void preloadCodeObjects() {
   preloadNetPartition();
@@ -899,6 +924,7 @@ inline void preloadCodeObjects() {
   preloadWire();
   preloadCollectives();
   preloadMaterialize();
+  preloadKindRows();
   preloadDatagen();
 }
 

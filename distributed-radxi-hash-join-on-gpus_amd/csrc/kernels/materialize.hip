@@ -146,7 +146,10 @@ using u64x2 = unsigned long long __attribute__((ext_vector_type(2)));
 // rows out of the XCD's L2 (FETCH_SIZE showed 64 B fetched per A access: no
 // reuse survived the B stream).  Write-through (`sc1`, `sc1 nt`) output
 // stores that leave L2 at once measured no faster (31.5 / 31.0 vs 30.9 ms).
-template <bool NT, bool XCD, bool BNT = false>
+// NULLS (outer-join rows): either rid of a pair may be NULL_RID; that side's
+// lanes load nothing and stage NULL_RID words.  The instantiations without it
+// are the code they were.
+template <bool NT, bool XCD, bool BNT = false, bool NULLS = false>
 __global__ __launch_bounds__(MT) void materializeLocalKernel(const ulonglong2 *__restrict__ pairs, uint64_t n,
                                                              const ulonglong2 *__restrict__ rowsA, uint64_t offA,
                                                              const ulonglong2 *__restrict__ rowsB, uint64_t offB,
@@ -174,8 +177,13 @@ __global__ __launch_bounds__(MT) void materializeLocalKernel(const ulonglong2 *_
       const uint32_t j = (lane >> 1) + 32 * k;  // pair whose row half this lane moves
       const uint64_t x = __shfl(p.x, j, 64), y = __shfl(p.y, j, 64);
       if (j < m) {
-        ra[k] = rowsA[2 * (x - offA) + half];
-        if (BNT) {
+        if (NULLS && x == NULL_RID)
+          ra[k] = make_ulonglong2(NULL_RID, NULL_RID);
+        else
+          ra[k] = rowsA[2 * (x - offA) + half];
+        if (NULLS && y == NULL_RID) {
+          rb[k] = make_ulonglong2(NULL_RID, NULL_RID);
+        } else if (BNT) {
           const u64x2 v = __builtin_nontemporal_load(reinterpret_cast<const u64x2 *>(rowsB + 2 * (y - offB) + half));
           rb[k] = make_ulonglong2(v.x, v.y);
         } else {
@@ -214,13 +222,24 @@ __global__ __launch_bounds__(MT) void materializeLocalKernel(const ulonglong2 *_
 }
 
 void materializeLocal(const ulonglong2 *pairs, uint64_t n, const uint64_t *rowsA, uint64_t offA,
-                      const uint64_t *rowsB, uint64_t offB, uint64_t *out, hipStream_t s, uint32_t variant) {
+                      const uint64_t *rowsB, uint64_t offB, uint64_t *out, hipStream_t s, uint32_t variant,
+                      bool nulls) {
   if (!n) return;
   const uint64_t blocks = ceilDiv(ceilDiv(n, 64), MAT_WAVES);
   const uint32_t grid = (uint32_t)(blocks < 8192 ? (blocks + 7) / 8 * 8 : 8192);
   const auto *ra = reinterpret_cast<const ulonglong2 *>(rowsA);
   const auto *rb = reinterpret_cast<const ulonglong2 *>(rowsB);
   auto *o = reinterpret_cast<ulonglong2 *>(out);
+  if (nulls) {
+    switch (variant) {
+      case 0: hipLaunchKernelGGL((materializeLocalKernel<true, true, false, true>), dim3(grid), dim3(MT), 0, s, pairs, n, ra, offA, rb, offB, o); break;
+      case 2: hipLaunchKernelGGL((materializeLocalKernel<false, true, true, true>), dim3(grid), dim3(MT), 0, s, pairs, n, ra, offA, rb, offB, o); break;
+      case 3: hipLaunchKernelGGL((materializeLocalKernel<false, true, false, true>), dim3(grid), dim3(MT), 0, s, pairs, n, ra, offA, rb, offB, o); break;
+      default: hipLaunchKernelGGL((materializeLocalKernel<true, true, true, true>), dim3(grid), dim3(MT), 0, s, pairs, n, ra, offA, rb, offB, o); break;
+    }
+    HIP_CHECK_LAUNCH();
+    return;
+  }
   switch (variant) {  // sweep: NT stores / non-temporal B loads
     case 0: hipLaunchKernelGGL((materializeLocalKernel<true, true, false>), dim3(grid), dim3(MT), 0, s, pairs, n, ra, offA, rb, offB, o); break;
     case 2: hipLaunchKernelGGL((materializeLocalKernel<false, true, true>), dim3(grid), dim3(MT), 0, s, pairs, n, ra, offA, rb, offB, o); break;

@@ -44,6 +44,7 @@
 //   markPlaceKernel            72 VGPRs (all layouts), no LDS
 #include "kernels.h"
 #include "device_common.h"
+#include "mark_units.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -56,9 +57,7 @@ constexpr int MK_K = 16;  // tuples per thread per batch (as the counting build/
 constexpr uint32_t MK_EMPTY32 = 0xFFFFFFFFu;
 constexpr unsigned long long MK_EMPTY64 = ~0ull;
 
-enum MarkLayout : int { MK_COMPRESSED = 0, MK_SPLIT = 1, MK_WIDE = 2 };
-
-static int markLayout(const BPArgs &a) { return a.wide ? MK_WIDE : a.split ? MK_SPLIT : MK_COMPRESSED; }
+// (MarkLayout, unitRange, unitSelect and markRid: mark_units.h, shared with kind_rows.hip)
 
 template <int LAYOUT>
 struct MarkKey {
@@ -209,22 +208,6 @@ __global__ __launch_bounds__(MK_T) void markEmitUnitsKernel(uint32_t P, const ui
   }
 }
 
-// Positions [ub, ue) of unit u (ue > ub: units are emitted for non-empty runs only).
-__device__ __forceinline__ void unitRange(const BPArgs &a, const MarkUnit u, uint64_t &ub, uint64_t &ue) {
-  ub = a.partS[u.part] + (uint64_t)u.chunk * a.sChunk;
-  ue = min(a.partSEnd[u.part], ub + a.sChunk);
-}
-
-// Selected positions of mark word w within [ub, ue): marked (semi) or unmarked (anti).
-__device__ __forceinline__ unsigned long long unitSelect(const unsigned long long *__restrict__ marks, uint64_t w,
-                                                         uint64_t ub, uint64_t ue, bool anti) {
-  unsigned long long valid = ~0ull;
-  if (w == (ub >> 6)) valid &= ~0ull << (ub & 63);
-  if (w == ((ue - 1) >> 6)) valid &= ~0ull >> (63 - ((ue - 1) & 63));
-  const unsigned long long m = marks[w];
-  return (anti ? ~m : m) & valid;
-}
-
 __global__ __launch_bounds__(MK_T) void markCountKernel(BPArgs a, const MarkUnit *__restrict__ units,
                                                        const uint32_t *__restrict__ nUnitsPtr, uint32_t capacity,
                                                        const unsigned long long *__restrict__ marks, bool anti,
@@ -248,16 +231,6 @@ __global__ __launch_bounds__(MK_T) void markCountKernel(BPArgs a, const MarkUnit
   }
   const unsigned long long total = blockReduceSum<MK_T, unsigned long long>(mine, wsum);
   if (threadIdx.x == 0 && total) atomicAdd(a.result, total);
-}
-
-template <int LAYOUT>
-__device__ __forceinline__ unsigned long long markRid(const BPArgs &a, uint64_t pos, uint64_t ridMask) {
-  if constexpr (LAYOUT == MK_SPLIT)
-    return reinterpret_cast<const uint32_t *>(a.S)[pos];
-  else if constexpr (LAYOUT == MK_COMPRESSED)
-    return reinterpret_cast<const unsigned long long *>(a.S)[pos] & ridMask;
-  else
-    return reinterpret_cast<const unsigned long long *>(a.S)[2 * pos + 1];
 }
 
 // One wave per unit.  Per round a lane reads one of the unit's next 64 mark

@@ -814,6 +814,32 @@ bool HashJoin::canFuseRows() const {
          plan.splitLocal && !plan.wide;
 }
 
+bool HashJoin::canFuseKindRows() const {
+  if (!ctx->onDevice() || ctx->comm()->size() != 1 || !plan.materialize || plan.bitmapSet || !plan.variants.kindRows ||
+      passes > 1)
+    return false;
+  if (core::isRidKind(plan.kind)) return true;  // every layout markPlace supports
+  // The matched rows need the fused row kernels (split layout); on by request only: the unfused rows measured faster.
+  return core::isOuterKind(plan.kind) && plan.variants.kindRows == 1 && plan.splitLocal && !plan.wide;
+}
+
+void HashJoin::setKindRowSink(const kernels::RowSink &s) {
+  JOIN_ASSERT(plan.kind != core::JoinKind::Inner, "HashJoin",
+              "setKindRowSink is the row sink of semi, anti and outer joins; kind = inner takes setRowSink");
+  JOIN_ASSERT(ctx->comm()->size() == 1, "HashJoin",
+              "join_rows: payload rows of a kind = %s join need a single rank (world size %u): a NULL rid has no "
+              "owner to fetch a row from",
+              core::joinKindName(plan.kind), ctx->comm()->size());
+  const uint64_t off[2] = {s.offA, s.offB}, rows[2] = {s.rowsAN, s.rowsBN};
+  for (int r = core::isRidKind(plan.kind) ? 1 : 0; r < 2; ++r)  // semi / anti: the inner payload is never read
+    JOIN_ASSERT(ridLo[r] > ridHi[r] || (ridLo[r] >= off[r] && ridHi[r] - off[r] < rows[r]), "HashJoin",
+                "kind row sink: %s payload rows [%lu, %lu) do not cover this rank's rids [%lu, %lu]",
+                r ? "outer" : "inner", (unsigned long)off[r], (unsigned long)(off[r] + rows[r]),
+                (unsigned long)ridLo[r], (unsigned long)ridHi[r]);
+  sink = s;
+  hasSink = true;
+}
+
 JoinResult HashJoin::run() {
   // Watchdog context: an injected stall (HPCJOIN_STALL) waits on this join's
   // communicator, and a timed-out wait names the phase the join was in.
@@ -915,7 +941,7 @@ JoinResult HashJoin::runImpl() {
   run.t3 = nowUs();
 
   // --------------------------------------------- local pass and build/probe
-  LocalPhase local(env, localOverflowed, hasSink && canFuseRows() ? &sink : nullptr);
+  LocalPhase local(env, localOverflowed, hasSink && (canFuseRows() || canFuseKindRows()) ? &sink : nullptr);
   local.run(run, result);
   const uint64_t t4 = nowUs();
   ctx->timeline().resolve();  // every stream was synchronised above

@@ -115,6 +115,20 @@ class HashJoin {
   // Throws unless the sink's payload columns cover this rank's rids of both
   // relations (the fused kernel indexes rows by rid - offset on the device).
   void setRowSink(const kernels::RowSink &s);
+  // Payload rows of a semi, anti or outer join (N = 1).  While a kind row sink
+  // is set and canFuseKindRows() holds, the place pass writes whole rows to
+  // the sink (kernels::markPlaceRows; outer kinds: the matched rows through
+  // the fused row path of the inner join) and leaves no rid / pair list.
+  // Semi / anti: 5-word rows {rid, outer row}, rowsA is not read; outer
+  // kinds: the 10-word rows of an inner join, a missing side all NULL_RID.
+  // canFuseKindRows(): device, N = 1, materialize, not the set-bitmap plan,
+  // variants.kindRows on; semi / anti in every layout, outer kinds over the
+  // split layout (where canFuseRows() would hold for an inner join) and only
+  // with variants.kindRows = 1 (the default, 2, keeps them unfused: faster).
+  bool canFuseKindRows() const;
+  // Throws for kind Inner (setRowSink is its sink), for N > 1, and unless the
+  // payload columns cover this rank's rids (semi / anti: the outer side only).
+  void setKindRowSink(const kernels::RowSink &s);
   // Smallest / largest rid of this rank's slice of relation 0 (inner) or 1
   // (outer); lo > hi for an empty slice.
   uint64_t ridMin(int which) const { return ridLo[which]; }

@@ -95,6 +95,8 @@ void BuildProbe::configure() {
 // redo after a sampled local pass overflowed) starts from clean marks.
 // The rid list is bounded by the outer tuples of this rank's window: it
 // cannot overflow, so there is no output re-run.
+// With a row sink on a device join the place pass writes the payload rows
+// {rid, outer row} to the sink (kernels::markPlaceRows) and no rid list is kept.
 void BuildProbe::executeMarks() {
   const bool dev = ctx->onDevice();
   const bool anti = plan.kind == core::JoinKind::Anti;
@@ -107,9 +109,10 @@ void BuildProbe::executeMarks() {
   const uint64_t words = kernels::markWords(windows[1]->getPartitionedCapacity());
   auto *marks = ws.getArray<unsigned long long>(words);
   ctx->zero(marks, words * 8);
-  outputCapacity = outerPartitionSize;
+  fused = plan.materialize && sink && dev;
+  outputCapacity = fused ? sink->capacity : outerPartitionSize;
   outRids = nullptr;
-  if (plan.materialize) outRids = ws.getArray<uint64_t>(outputCapacity + 1);
+  if (plan.materialize && !fused) outRids = ws.getArray<uint64_t>(outputCapacity + 1);
   if (!dev) {
     tl.begin("BPTASKTIME");
     tl.beginSplit("BPKERNEL", "BPBUILD", wb, "BPPROBE", wp);
@@ -165,8 +168,12 @@ void BuildProbe::executeMarks() {
   kernels::markCount(uargs, units, nUnits, unitCapacity, marks, anti, unitCounts, s);  // -> counters[0]
   if (plan.materialize) {
     kernels::scanExclusiveU32to64(unitCounts, unitOffsets, unitCapacity, args.outCursor, scanWs, s);
-    kernels::markPlace(uargs, units, nUnits, unitCapacity, marks, anti, unitOffsets,
-                       reinterpret_cast<unsigned long long *>(outRids), outputCapacity, s);
+    if (fused)
+      kernels::markPlaceRows(uargs, units, nUnits, unitCapacity, marks, anti, unitOffsets, nullptr, nullptr,
+                             kernels::KindRowShape::Rid, sink->rowsB, sink->offB, sink->out, outputCapacity, s);
+    else
+      kernels::markPlace(uargs, units, nUnits, unitCapacity, marks, anti, unitOffsets,
+                         reinterpret_cast<unsigned long long *>(outRids), outputCapacity, s);
   }
   hipEvent_t done = tl.mark(s);
   tl.endAt("BPKERNEL", done);
@@ -182,6 +189,11 @@ void BuildProbe::executeMarks() {
 // and unit counts are zeroed here, so every re-run (item-list or output
 // overflow in collect(), the exact redo after a sampled local pass
 // overflowed) starts from clean marks.
+// With a row sink on a device join over the split layout the place pass writes
+// whole rows to the sink: the matched pairs' rows through the inner join's
+// fused row kernels, the NULL-padded rows behind them by
+// kernels::markPlaceRows, from the same bases as the pairs.  The sink is the
+// caller's: an overflow is reported, not re-run.
 void BuildProbe::executeOuter() {
   const bool dev = ctx->onDevice();
   const bool keepR = core::preservesInner(plan.kind), keepS = core::preservesOuter(plan.kind);
@@ -198,7 +210,16 @@ void BuildProbe::executeOuter() {
   if (keepS) ctx->zero(marksS, wordsS * 8);
   outPairs = nullptr;
   args.materialize = plan.materialize;
-  if (plan.materialize) {
+  fused = plan.materialize && sink && dev && args.split && !args.wide;
+  if (fused) {
+    outputCapacity = sink->capacity;
+    args.outRows = reinterpret_cast<ulonglong2 *>(sink->out);
+    args.rowsA = reinterpret_cast<const ulonglong2 *>(sink->rowsA);
+    args.rowsB = reinterpret_cast<const ulonglong2 *>(sink->rowsB);
+    args.offA = sink->offA;
+    args.offB = sink->offB;
+    args.outCapacity = outputCapacity;
+  } else if (plan.materialize) {
     // The unmatched rows alone never overflow the default; the pairs can (repeated keys): collect() grows it.
     if (outputCapacity == 0) outputCapacity = outerPartitionSize + 1024 + (keepR ? innerPartitionSize : 0);
     outPairs = static_cast<ulonglong2 *>(ws.get(outputCapacity * sizeof(ulonglong2)));
@@ -321,10 +342,18 @@ void BuildProbe::executeOuter() {
     args.result = counters + 3;  // the count pass already counted
     kernels::buildProbe(args, items, nItems, capacity, s);  // the inner join's place pass, unchanged
     // Unmatched rows behind the pairs: inner side from [1], outer side from [1] + [4] ([4] = 0 unless R is preserved).
-    if (keepR)
+    if (keepR && fused)
+      kernels::markPlaceRows(side[0].a, side[0].units, nUnitsR, side[0].cap, marksR, true, side[0].unitOffsets,
+                             counters + 1, nullptr, kernels::KindRowShape::InnerPad, sink->rowsA, sink->offA, sink->out,
+                             outputCapacity, s);
+    else if (keepR)
       kernels::markPlacePairs(side[0].a, side[0].units, nUnitsR, side[0].cap, marksR, side[0].unitOffsets, counters + 1,
                               nullptr, true, outPairs, outputCapacity, s);
-    if (keepS)
+    if (keepS && fused)
+      kernels::markPlaceRows(side[1].a, side[1].units, nUnitsS, side[1].cap, marksS, true, side[1].unitOffsets,
+                             counters + 1, counters + 4, kernels::KindRowShape::OuterPad, sink->rowsB, sink->offB,
+                             sink->out, outputCapacity, s);
+    else if (keepS)
       kernels::markPlacePairs(side[1].a, side[1].units, nUnitsS, side[1].cap, marksS, side[1].unitOffsets, counters + 1,
                               counters + 4, false, outPairs, outputCapacity, s);
   }
@@ -539,8 +568,12 @@ bool BuildProbe::collect() {
                   (unsigned long)h[1], (unsigned long)h[0]);
     }
     if (plan.materialize && outputCount > outputCapacity) {
-      outputCapacity = outputCount;
-      again = true;
+      if (fused) {
+        overflowOut = true;  // the buffer is the caller's: it re-runs with a larger one
+      } else {
+        outputCapacity = outputCount;
+        again = true;
+      }
     }
     return again;
   }
@@ -552,6 +585,7 @@ bool BuildProbe::collect() {
     JOIN_ASSERT(nUnits <= unitCapacity, "BuildProbe", "%u outer units, bound %u", nUnits, unitCapacity);
     JOIN_ASSERT(!plan.materialize || outputCount == matches, "BuildProbe",
                 "semi/anti join placed %lu rids but counted %lu", (unsigned long)outputCount, (unsigned long)matches);
+    if (fused && outputCount > outputCapacity) overflowOut = true;  // a sink smaller than the outer side
     if (nItems > capacity) {
       capacity = nItems;
       return true;

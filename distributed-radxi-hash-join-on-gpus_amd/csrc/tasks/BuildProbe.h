@@ -11,6 +11,10 @@
 // the hit marks of the preserved sides) -> markCount(anti) over the units of
 // each preserved side -> (materialize) scans -> the inner join's place pass
 // -> markPlacePairs appends the NULL-padded rows (kernels/outer_join.hip).
+// With a row sink (HashJoin::setKindRowSink, device, N = 1) the place pass of
+// those kinds writes payload rows instead: markPlaceRows in place of markPlace
+// / markPlacePairs, and for outer kinds over the split layout the inner join's
+// fused row kernels for the matched pairs (kernels/kind_rows.hip).
 // The host reads the counters once, after the join's single final sync.
 #pragma once
 
@@ -60,7 +64,9 @@ class BuildProbe : public Task {
   bool outputOverflowed() const { return overflowOut; }
   // Fused row output (device, split layout): the materialize pass writes whole
   // rows to the sink.  A sink overflow is reported, not re-run (the caller
-  // owns the buffer).
+  // owns the buffer).  Semi / anti and outer kinds (device): the place pass
+  // writes their payload rows to the sink (kernels::markPlaceRows) and no rid
+  // or pair list is kept.
   void setRowSink(const kernels::RowSink *s) { sink = s; }
   // Pairs go to this pinned host buffer (JoinConfig::outputHost, outputCapacity
   // pairs); an overflow is reported, not re-run.

@@ -8,6 +8,8 @@ host twins (CPU tensors).  Tuples are int64 tensors of shape [n, 2] holding
     join_count(R, S)                                      # whole engine
     semi_join(R, S), anti_join(R, S)                      # outer rids with / without an inner partner
     left_outer_join(R, S), right_outer_join(R, S), full_outer_join(R, S)   # pairs + NULL_RID-padded rows
+    semi_join_rows(R, S, S_rows), anti_join_rows(R, S, S_rows)            # [m, 5]: outer rid + its payload row
+    full_outer_join_rows(R, S, R_rows, S_rows)                            # [m, 10]: rids + both rows, NULL_RID-padded
 """
 from __future__ import annotations
 
@@ -79,6 +81,39 @@ def build_probe_outer(R, S, part_r, part_s, frag_shift: int, key_shift: int, wid
     position of R / S: the tuple has a partner; all false for a side not kept)."""
     return _C().ops.build_probe_outer(R, S, part_r, part_s, frag_shift, key_shift, wide, r_chunk, s_chunk,
                                       keep_inner, keep_outer)
+
+
+def build_probe_mark_rows(R, S, part_r, part_s, frag_shift: int, key_shift: int, wide=False, r_chunk=4096,
+                          s_chunk=65536, outer_rows=None, rid_offset=0, out_capacity=0) -> dict:
+    """``build_probe_marks`` with the row-writing place pass: ``semi_rows`` / ``anti_rows`` are the whole
+    ``[capacity + guard_rows, 5]`` buffers (``capacity`` = ``out_capacity`` or ``len(S)``) holding
+    ``[rid, outer_rows[rid - rid_offset]]`` per selected tuple below the capacity and ``sentinel`` words everywhere
+    else; ``semi_count`` / ``anti_count`` are the full counts."""
+    return _C().ops.build_probe_mark_rows(R, S, part_r, part_s, frag_shift, key_shift, wide, r_chunk, s_chunk,
+                                          outer_rows, rid_offset, out_capacity)
+
+
+def build_probe_outer_rows(R, S, part_r, part_s, frag_shift: int, key_shift: int, wide=False, r_chunk=4096,
+                           s_chunk=65536, keep_inner=True, keep_outer=True, inner_rows=None, inner_rid_offset=0,
+                           outer_rows=None, outer_rid_offset=0) -> dict:
+    """``build_probe_outer`` plus ``rows``: the whole ``[m + guard_rows, 10]`` buffer with the 10-word row of
+    every pair and, behind them, the NULL_RID-padded rows of the kept sides written by the row-writing place
+    pass; ``sentinel`` words in the guard rows."""
+    return _C().ops.build_probe_outer_rows(R, S, part_r, part_s, frag_shift, key_shift, wide, r_chunk, s_chunk,
+                                           keep_inner, keep_outer, inner_rows, inner_rid_offset, outer_rows,
+                                           outer_rid_offset)
+
+
+def rid_rows(rids: torch.Tensor, rows: torch.Tensor, rid_offset: int = 0) -> torch.Tensor:
+    """int64 [n, 5]: ``[rid, rows[rid - rid_offset]]`` per rid."""
+    return _C().ops.rid_rows(rids.contiguous(), rows, rid_offset)
+
+
+def pair_rows(pairs: torch.Tensor, rows_a: torch.Tensor, off_a: int, rows_b: torch.Tensor, off_b: int,
+              variant: int = 1) -> torch.Tensor:
+    """int64 [n, 10]: ``[rid_a, rid_b, rows_a[rid_a - off_a], rows_b[rid_b - off_b]]`` per pair; a ``NULL_RID``
+    side gives four ``NULL_RID`` words and reads no row."""
+    return _C().ops.pair_rows(pairs.contiguous(), rows_a, off_a, rows_b, off_b, variant)
 
 
 def npj_count(R: torch.Tensor, S: torch.Tensor) -> int:
@@ -189,3 +224,54 @@ def right_outer_join_count(inner: torch.Tensor, outer: torch.Tensor, config=None
 def full_outer_join_count(inner: torch.Tensor, outer: torch.Tensor, config=None) -> int:
     """Rows of ``full_outer_join``."""
     return _outer_join(inner, outer, "FULL_OUTER", False, config)
+
+
+def _kind_join_rows(inner, outer, kind: str, inner_rows, outer_rows, rid_offset: int, config=None) -> torch.Tensor:
+    C = _C()
+    cfg = config or C.JoinConfig()
+    cfg.kind = getattr(C.JoinKind, kind)
+    cfg.materialize = True
+    on_dev = inner.is_cuda
+    ctx = C.ExecContext("device" if on_dev else "host", (inner.device.index or 0) if on_dev else -1,
+                        C.LocalCommunicator())
+    R = C.Relation.from_tensor(inner.contiguous(), inner.shape[0])
+    S = C.Relation.from_tensor(outer.contiguous(), outer.shape[0])
+    j = C.HashJoin(R, S, ctx, cfg)
+    if inner_rows is None:  # semi / anti: the inner payload is never read
+        inner_rows = torch.empty((0, 4), dtype=torch.int64, device=outer_rows.device)
+    _, rows = j.join_rows(ctx, inner_rows, rid_offset, inner_rows.shape[0], outer_rows, rid_offset,
+                          outer_rows.shape[0])
+    return rows
+
+
+def semi_join_rows(inner: torch.Tensor, outer: torch.Tensor, outer_rows: torch.Tensor, rid_offset: int = 0,
+                   config=None) -> torch.Tensor:
+    """int64 [m, 5]: ``[outer rid, outer_rows[rid - rid_offset]]`` of the outer tuples whose key occurs in
+    ``inner``, each once, any order."""
+    return _kind_join_rows(inner, outer, "SEMI", None, outer_rows, rid_offset, config)
+
+
+def anti_join_rows(inner: torch.Tensor, outer: torch.Tensor, outer_rows: torch.Tensor, rid_offset: int = 0,
+                   config=None) -> torch.Tensor:
+    """int64 [m, 5]: ``[outer rid, outer row]`` of the outer tuples whose key does not occur in ``inner``."""
+    return _kind_join_rows(inner, outer, "ANTI", None, outer_rows, rid_offset, config)
+
+
+def left_outer_join_rows(inner: torch.Tensor, outer: torch.Tensor, inner_rows: torch.Tensor,
+                         outer_rows: torch.Tensor, rid_offset: int = 0, config=None) -> torch.Tensor:
+    """int64 [m, 10]: ``[rid_inner, rid_outer, inner row, outer row]`` of ``left_outer_join``'s rows; the outer
+    half of an unmatched inner tuple's row is five ``NULL_RID`` words.  Both payloads start at ``rid_offset``."""
+    return _kind_join_rows(inner, outer, "LEFT_OUTER", inner_rows, outer_rows, rid_offset, config)
+
+
+def right_outer_join_rows(inner: torch.Tensor, outer: torch.Tensor, inner_rows: torch.Tensor,
+                          outer_rows: torch.Tensor, rid_offset: int = 0, config=None) -> torch.Tensor:
+    """int64 [m, 10]: the rows of ``right_outer_join``; the inner half of an unmatched outer tuple's row is
+    ``NULL_RID`` words."""
+    return _kind_join_rows(inner, outer, "RIGHT_OUTER", inner_rows, outer_rows, rid_offset, config)
+
+
+def full_outer_join_rows(inner: torch.Tensor, outer: torch.Tensor, inner_rows: torch.Tensor,
+                         outer_rows: torch.Tensor, rid_offset: int = 0, config=None) -> torch.Tensor:
+    """int64 [m, 10]: the rows of ``full_outer_join``, NULL_RID-padded on either side."""
+    return _kind_join_rows(inner, outer, "FULL_OUTER", inner_rows, outer_rows, rid_offset, config)

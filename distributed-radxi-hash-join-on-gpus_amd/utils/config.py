@@ -11,7 +11,7 @@ _FIELDS = ["network_bits", "local_bits", "two_level", "key_shift", "materialize"
            "split_local", "direct_count", "split_histogram", "pipeline_outer", "bitmap_join", "semi_bitmap", "skew_split",
            "reserve_workspace", "passes", "workspace_budget", "link_gbps_per_peer", "codec_extra_ps_per_tuple",
            # kernel-shape variants (sweeps / A-B tests; JoinConfig.variants in C++)
-           "bm_threads", "bm_flat", "reduce_chunks", "key_count", "rows_lds", "mat_variant"]
+           "bm_threads", "bm_flat", "reduce_chunks", "key_count", "rows_lds", "mat_variant", "kind_rows"]
 _FLOATS = ("link_gbps_per_peer", "codec_extra_ps_per_tuple")
 _BOOLS = ("two_level", "materialize", "checks", "split_local", "direct_count", "split_histogram", "pipeline_outer",
           "bitmap_join", "semi_bitmap", "skew_split", "reserve_workspace")
