@@ -6,13 +6,16 @@
 //               [--rank R --world W --id-file PATH]   (one process per GPU; rank 0
 //                                                      writes the ncclUniqueId to PATH)
 //               [--chunks C] [--net-bits B] [--local-bits B] [--materialize] [--wide]
-//               [--round-robin] [--perf-dir DIR] [--kind inner|semi|anti|left|right|full]
+//               [--round-robin] [--perf-dir DIR] [--kind inner|semi|anti|left|right|full|group]
 //               [--inner-domain D] [--outer-domain D] [--outer-key-offset K] [--semi-bitmap]
 // --semi-bitmap: JoinConfig::semiBitmap (--kind semi|anti on one rank: the
 // set-semantics bitmap plan; the [INFO] plan line then says bitmapSet).
 // --kind semi|anti: `matches` is the number of outer tuples with / without an
 // inner partner; --kind left|right|full: the number of result rows (the inner
-// join's pairs plus the unmatched tuples of the preserved sides).  `correct`
+// join's pairs plus the unmatched tuples of the preserved sides); --kind group:
+// `matches` is `matched_pairs`, the sum of the per-inner-tuple counts (the
+// inner join's count), printed with `groups` (result rows: the inner tuples)
+// and `empty_groups` (rows with count 0).  `correct`
 // is checked against a host oracle computed here when that is cheap (one
 // rank, at most 64M tuples in all), else omitted.
 // --inner-domain D: inner keys UNIFORM over D keys (repeated and missing
@@ -90,8 +93,9 @@ int main(int argc, char **argv) {
       else if (k == "left") cfg.kind = core::JoinKind::LeftOuter;
       else if (k == "right") cfg.kind = core::JoinKind::RightOuter;
       else if (k == "full") cfg.kind = core::JoinKind::FullOuter;
+      else if (k == "group") cfg.kind = core::JoinKind::Group;
       else {
-        std::fprintf(stderr, "unknown --kind %s (inner|semi|anti|left|right|full)\n", k.c_str());
+        std::fprintf(stderr, "unknown --kind %s (inner|semi|anti|left|right|full|group)\n", k.c_str());
         return 2;
       }
     }
@@ -196,7 +200,8 @@ int main(int argc, char **argv) {
       for (const auto &kc : copies)
         if (!probed.count(kc.first)) unmatchedInner += kc.second;
       switch (cfg.kind) {
-        case core::JoinKind::Inner: expected = pairs; break;
+        case core::JoinKind::Inner:
+        case core::JoinKind::Group: expected = pairs; break;  // group: the counts add up to the pairs
         case core::JoinKind::Semi: expected = semi; break;
         case core::JoinKind::Anti: expected = outer - semi; break;
         default:
@@ -212,7 +217,7 @@ int main(int argc, char **argv) {
   for (int w = 0; w < warmup; ++w) join.run();
   ctx.resetScratch();  // grow the arena to the warmup peak before timing
   std::vector<double> times;
-  uint64_t matches = 0;
+  uint64_t matches = 0, groupTotals[3] = {0, 0, 0};  // group: matched pairs, groups, empty groups (all ranks)
   for (int it = 0; it < iters; ++it) {
     comm->barrier();
     operators::JoinResult r = join.run();
@@ -220,6 +225,13 @@ int main(int argc, char **argv) {
     comm->allGatherHost(mine.data(), all.data(), 1);
     times.push_back(*std::max_element(all.begin(), all.end()) / 1000.0);
     matches = r.globalMatches;
+    if (cfg.kind == core::JoinKind::Group) {
+      groupTotals[0] = r.matchedPairs;
+      groupTotals[1] = r.localMatches;
+      groupTotals[2] = r.unmatchedInner;
+      comm->allReduceSumHost(groupTotals, 3);
+      matches = groupTotals[0];
+    }
   }
   performance::Measurements::printMeasurements(comm.get());
   performance::Measurements::storeAllMeasurements();
@@ -230,6 +242,9 @@ int main(int argc, char **argv) {
                 "\"ms_per_join\": %.3f, \"matches\": %lu",
                 med > 0 ? (inner + outer) / (med * 1e6) : 0.0, world, med, (unsigned long)matches);
     if (cfg.kind != core::JoinKind::Inner) std::printf(", \"kind\": \"%s\"", core::joinKindName(cfg.kind));
+    if (cfg.kind == core::JoinKind::Group)
+      std::printf(", \"matched_pairs\": %lu, \"groups\": %lu, \"empty_groups\": %lu", (unsigned long)groupTotals[0],
+                  (unsigned long)groupTotals[1], (unsigned long)groupTotals[2]);
     if (cfg.kind == core::JoinKind::Inner || expected != UINT64_MAX)  // semi / anti without an oracle: omitted
       std::printf(", \"expected\": %s%lu, \"correct\": %s", expected == UINT64_MAX ? "-" : "",
                   (unsigned long)(expected == UINT64_MAX ? 0 : expected),

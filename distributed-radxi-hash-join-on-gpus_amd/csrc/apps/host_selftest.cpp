@@ -41,16 +41,23 @@ struct Case {
   core::JoinKind kind = core::JoinKind::Inner;
   // semi / anti on the set-semantics bitmap plan (JoinConfig::semiBitmap): one rank, the plan must be taken
   bool semiBitmap = false;
+  // kind Group: sum an outer value column per group (HashJoin::joinGroup; one rank), else counts only
+  bool groupValues = false;
 };
 
+// The value of outer tuple `rid` in the group-join cases: spread over the int64 range, so the sums wrap.
+uint64_t groupValue(uint64_t rid) { return kernels::mix64(rid + 77) * 0x9E3779B97F4A7C15ull; }
+
 bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
-  if (c.semiBitmap) ranks = 1;
+  if (c.semiBitmap || c.groupValues) ranks = 1;
   auto group = std::make_shared<comm::InProcessGroup>(ranks);
   std::vector<std::string> errors(ranks);
   std::vector<uint64_t> matches(ranks, 0), pairs(ranks, 0);
   std::vector<std::vector<uint64_t>> rids(ranks);
   std::vector<std::vector<std::pair<uint64_t, uint64_t>>> rows(ranks);
   const bool inner = c.kind == core::JoinKind::Inner, outerKind = core::isOuterKind(c.kind);
+  const bool groupKind = c.kind == core::JoinKind::Group;
+  std::vector<std::vector<uint64_t>> groups(ranks);  // group rows, 2 or 3 words each
   data::GenSpec is, os;
   is.seed = 11;
   is.tpchSparse = c.tpch;
@@ -83,13 +90,33 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
       operators::HashJoin j(&R, &S, &ctx, cfg);
       if (c.semiBitmap && !(j.getPlan().bitmapJoin && j.getPlan().bitmapSet))
         throw std::runtime_error("the set bitmap plan was not taken");
-      operators::JoinResult res = j.run();
+      std::vector<uint64_t> values;
+      if (c.groupValues) {  // strided column: word 1 of 3-word rows, rids from 0 (one rank)
+        values.assign(3 * GS, 0);
+        for (uint64_t i = 0; i < GS; ++i) values[3 * i + 1] = groupValue(i);
+      }
+      operators::JoinResult res = c.groupValues ? j.joinGroup(values.data() + 1, 0, GS, 3) : j.run();
+      if (groupKind) {
+        const uint64_t W = c.groupValues ? 3 : 2;
+        if (res.localMatches != res.outputGroups || res.unmatchedOuter != 0 || res.outputPairs != 0 ||
+            res.outputRids != 0 || res.groupSums != c.groupValues || !j.getOutputGroups())
+          throw std::runtime_error("group join: the result fields do not add up");
+        groups[r].assign(j.getOutputGroups(), j.getOutputGroups() + res.outputGroups * W);
+        uint64_t pairsSum = 0, zeros = 0;
+        for (uint64_t i = 0; i < res.outputGroups; ++i) {
+          pairsSum += groups[r][i * W + 1];
+          zeros += groups[r][i * W + 1] == 0;
+        }
+        if (pairsSum != res.matchedPairs || zeros != res.unmatchedInner)
+          throw std::runtime_error("group join: matchedPairs / unmatchedInner differ from the rows");
+      }
       if (c.semiBitmap && !(res.bitmapJoin && res.localFallbacks == 0 && res.outputPairs == 0 &&
                             res.outputRids == (c.materialize ? res.localMatches : 0)))
         throw std::runtime_error("set bitmap plan: the result fields do not add up");
       matches[r] = res.globalMatches;
       pairs[r] = res.outputPairs;
-      if (outerKind) {
+      if (groupKind) {
+      } else if (outerKind) {
         if (res.localMatches != res.matchedPairs + res.unmatchedInner + res.unmatchedOuter ||
             res.outputPairs != (c.materialize ? res.localMatches : 0) || res.outputRids != 0)
           throw std::runtime_error("outer join: the result fields do not add up");
@@ -146,6 +173,8 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
         if (!probed.count(kv.first))
           for (uint64_t rid : kv.second) expectedRows.emplace(rid, kernels::NULL_RID);
     expected = expectedRows.size();
+  } else if (groupKind) {  // per inner tuple the count (and wrapping sum) of the outer tuples with its key
+    expected = G;
   } else if (!inner) {  // the outer tuples whose key is (semi) / is not (anti) among the inner keys
     data::Relation R(G, G, Location::Host, 0), S(GS, GS, Location::Host, 0);
     R.generate(is, 0);
@@ -176,7 +205,42 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
     if (!ok) std::printf("[%s] rows differ from the oracle (%lu distinct, expected %lu)\n", c.name,
                          (unsigned long)seen.size(), (unsigned long)expected);
   }
-  if (ok && c.materialize && !inner && !outerKind) {  // the ranks' rid lists together: the oracle set, no rid twice
+  if (ok && groupKind) {  // the ranks' rows together: every inner rid once, with the oracle's count and sum
+    data::Relation R(G, G, Location::Host, 0), S(GS, GS, Location::Host, 0);
+    R.generate(is, 0);
+    S.generate(os, 0);
+    std::unordered_map<uint64_t, std::pair<uint64_t, uint64_t>> byKey;  // outer key -> (count, sum)
+    for (uint64_t i = 0; i < GS; ++i) {
+      auto &e = byKey[S.getData()[i].key];
+      ++e.first;
+      e.second += groupValue(S.getData()[i].rid);
+    }
+    std::unordered_map<uint64_t, uint64_t> keyOf;  // inner rid -> key
+    for (uint64_t i = 0; i < G; ++i) keyOf[R.getData()[i].rid] = R.getData()[i].key;
+    const uint64_t W = c.groupValues ? 3 : 2;
+    std::unordered_set<uint64_t> seen;
+    uint64_t repeated = 0, empty = 0;
+    for (const auto &v : groups)
+      for (uint64_t i = 0; i + W <= v.size(); i += W) {
+        auto k = keyOf.find(v[i]);
+        if (k == keyOf.end() || !seen.insert(v[i]).second) {
+          ok = false;
+          continue;
+        }
+        auto e = byKey.find(k->second);
+        const uint64_t cnt = e == byKey.end() ? 0 : e->second.first, sum = e == byKey.end() ? 0 : e->second.second;
+        if (v[i + 1] != cnt || (c.groupValues && v[i + 2] != sum)) ok = false;
+        empty += cnt == 0;
+      }
+    if (seen.size() != G) ok = false;
+    std::unordered_map<uint64_t, uint64_t> copies;
+    for (uint64_t i = 0; i < G; ++i) ++copies[R.getData()[i].key];
+    for (const auto &kc : copies) repeated += kc.second > 1 ? kc.second : 0;
+    if (repeated * 5 < G || empty == 0) ok = false;  // the case must have repeated inner keys and empty groups
+    if (!ok) std::printf("[%s] group rows differ from the oracle (%lu distinct rids, expected %lu)\n", c.name,
+                         (unsigned long)seen.size(), (unsigned long)G);
+  }
+  if (ok && c.materialize && !inner && !outerKind && !groupKind) {  // the ranks' rid lists together: the oracle set, no rid twice
     std::unordered_set<uint64_t> seen;
     for (const auto &v : rids)
       for (uint64_t x : v)
@@ -254,6 +318,12 @@ int main(int argc, char **argv) {
        core::JoinKind::RightOuter},
       {"full_uniform_materialize", kernels::KeyDistribution::Uniform, false, true, false, core::KeyHashing::Auto, false,
        core::JoinKind::FullOuter},
+      {"group_zipf_count", kernels::KeyDistribution::Zipf, false, true, false, core::KeyHashing::Auto, true,
+       core::JoinKind::Group},
+      {"group_uniform_sum", kernels::KeyDistribution::Uniform, false, true, false, core::KeyHashing::Auto, false,
+       core::JoinKind::Group, false, true},
+      {"group_wide_sum", kernels::KeyDistribution::Zipf, true, true, false, core::KeyHashing::Auto, false,
+       core::JoinKind::Group, false, true},
       {"semi_bitmap_zipf_rids", kernels::KeyDistribution::Zipf, false, true, false, core::KeyHashing::Auto, false,
        core::JoinKind::Semi, true},
       {"semi_bitmap_uniform_count", kernels::KeyDistribution::Uniform, false, false, false, core::KeyHashing::Auto,

@@ -679,6 +679,116 @@ py::dict opBuildProbeOuterRows(const at::Tensor &R, const at::Tensor &S, const a
   return buildProbeOuterImpl(R, S, partR, partS, fragShift, keyShift, wide, rChunk, sChunk, keepInner, keepOuter, &pr);
 }
 
+// ---- group join over partition-major inputs: LDS counters / sums, inner units, rows ----
+// rows: int64 [|R|, 2] (inner rid, count) or, with values, [|R|, 3] (inner rid,
+// count, sum); counts / sums: the raw accumulators by position of R (int64;
+// sums all 0 without values) (kernels/group_join.hip and the host twins).
+py::dict opBuildProbeGroup(const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR, const at::Tensor &partS,
+                           int64_t fragShift, int64_t keyShift, bool wide, int64_t rChunk, int64_t sChunk,
+                           const c10::optional<at::Tensor> &values, int64_t ridOffset) {
+  TORCH_CHECK(R.device() == S.device(), "R and S must live on the same device");
+  TORCH_CHECK(rChunk >= 1 && sChunk >= 1, "r_chunk and s_chunk must be positive");
+  TORCH_CHECK((uint64_t)S.size(0) < (1ull << 32), "build_probe_group: the per-group counters are 32 bits wide");
+  setDevice(R);
+  const bool sum = values.has_value() && values->defined();
+  const unsigned long long *vals = nullptr;
+  uint64_t stride = 1;
+  if (sum) {
+    const at::Tensor &v = *values;
+    TORCH_CHECK(v.dim() == 1 && v.scalar_type() == at::kLong && v.device() == R.device(),
+                "build_probe_group: values must be a 1-D int64 tensor on the device of R and S");
+    TORCH_CHECK(v.size(0) == 0 || v.stride(0) >= 1, "build_probe_group: values need a positive element stride");
+    vals = reinterpret_cast<const unsigned long long *>(v.data_ptr());
+    stride = v.size(0) ? (uint64_t)v.stride(0) : 1;
+    if (S.size(0)) {  // every outer rid must have a value
+      at::Tensor rid = wide ? S.select(1, 1) : at::bitwise_and(S.reshape({-1}), keyShift >= 64 ? -1 : ((int64_t(1) << keyShift) - 1));
+      const int64_t lo = rid.min().item<int64_t>(), hi = rid.max().item<int64_t>();
+      TORCH_CHECK(lo >= ridOffset && hi - ridOffset < v.size(0), "build_probe_group: values [", ridOffset, ", ",
+                  ridOffset + v.size(0), ") do not cover the outer rids [", lo, ", ", hi, "]");
+    }
+  }
+  kernels::BPArgs a;
+  a.R = R.data_ptr();
+  a.S = S.data_ptr();
+  at::Tensor pr = partR.to(R.device()).contiguous(), ps = partS.to(R.device()).contiguous();
+  TORCH_CHECK(pr.size(0) == ps.size(0) && pr.size(0) >= 1, "part_r and part_s must have the same P + 1 entries");
+  a.partR = ptr<uint64_t>(pr);
+  a.partS = ptr<uint64_t>(ps);
+  a.P = (uint32_t)pr.size(0) - 1;
+  a.rChunk = (uint32_t)rChunk;
+  a.sChunk = (uint32_t)sChunk;
+  a.fragShift = (uint32_t)fragShift;
+  a.keyShift = (uint32_t)keyShift;
+  a.wide = wide;
+  const int64_t nR = R.size(0), nS = S.size(0), W = sum ? 3 : 2;
+  at::Tensor accCount = at::zeros({nR + 2}, like(R, at::kInt)), accSum = at::zeros({nR + 2}, like(R));
+  at::Tensor rows = at::empty({nR, W}, like(R));
+  uint64_t matched = 0, zeros = 0;
+  if (R.is_cuda()) {
+    at::Tensor ctr = at::zeros({8}, like(R));
+    auto *c = reinterpret_cast<unsigned long long *>(ctr.data_ptr());
+    a.result = c;
+    uint32_t *nItems = reinterpret_cast<uint32_t *>(c + 2), *nUnits = reinterpret_cast<uint32_t *>(c + 6);
+    const int64_t P1 = std::max<int64_t>(a.P, 1);
+    at::Tensor counts = at::empty({P1}, like(R, at::kInt)), offsets = at::empty({P1}, like(R, at::kInt));
+    kernels::BPArgs ua = kernels::outerSwapSides(a, std::min<uint32_t>(a.rChunk, kernels::MARK_UNIT));
+    ua.result = c + 4;
+    const uint32_t unitCap = a.P + (uint32_t)(nR / ua.sChunk) + 1;
+    uint32_t capacity = 2 * a.P + (uint32_t)(nS / a.sChunk + nR / a.rChunk) + 1024;
+    at::Tensor items, scanWs;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      items = at::empty({(int64_t)capacity * 2}, like(R));
+      scanWs = at::empty({(int64_t)kernels::scanWorkspaceBytes(std::max<uint64_t>(a.P, unitCap)) / 4 + 1},
+                         like(R, at::kInt));
+      ctr.zero_();
+      accCount.zero_();
+      accSum.zero_();
+      kernels::bpPlanCounts(a, ptr<uint32_t>(counts), nullptr);
+      kernels::scanExclusiveU32(ptr<uint32_t>(counts), ptr<uint32_t>(offsets), a.P, nItems, scanWs.data_ptr(), nullptr);
+      kernels::bpEmit(a, ptr<uint32_t>(counts), ptr<uint32_t>(offsets), ptr<kernels::BPItem>(items), capacity, nullptr);
+      kernels::bpGroup(a, ptr<kernels::BPItem>(items), nItems, capacity, vals, (uint64_t)ridOffset, stride,
+                       ptr<uint32_t>(accCount), sum ? ptr<unsigned long long>(accSum) : nullptr, nullptr);
+      HIP_CHECK(hipDeviceSynchronize());
+      const uint32_t need = (uint32_t)(ctr.cpu()[2].item<int64_t>() & 0xFFFFFFFF);
+      if (need <= capacity) break;
+      TORCH_CHECK(attempt == 0, "build_probe_group: the work-item list overflowed twice");
+      capacity = need;
+    }
+    at::Tensor units = at::empty({(int64_t)unitCap}, like(R)), unitCounts = at::zeros({(int64_t)unitCap}, like(R, at::kInt)),
+               unitOffsets = at::empty({(int64_t)unitCap}, like(R));
+    kernels::markPlanUnits(ua, ptr<uint32_t>(counts), nullptr);
+    kernels::scanExclusiveU32(ptr<uint32_t>(counts), ptr<uint32_t>(offsets), a.P, nUnits, scanWs.data_ptr(), nullptr);
+    kernels::markEmitUnits(ua, ptr<uint32_t>(counts), ptr<uint32_t>(offsets), ptr<kernels::MarkUnit>(units), unitCap,
+                           nullptr);
+    kernels::groupUnitLengths(ua, ptr<kernels::MarkUnit>(units), nUnits, unitCap, ptr<uint32_t>(unitCounts), nullptr);
+    kernels::scanExclusiveU32to64(ptr<uint32_t>(unitCounts), ptr<unsigned long long>(unitOffsets), unitCap, c + 1,
+                                  scanWs.data_ptr(), nullptr);
+    kernels::groupEmit(ua, ptr<kernels::MarkUnit>(units), nUnits, unitCap, ptr<uint32_t>(accCount),
+                       sum ? ptr<unsigned long long>(accSum) : nullptr, ptr<unsigned long long>(unitOffsets),
+                       ptr<unsigned long long>(rows), (uint64_t)nR, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    at::Tensor h = ctr.cpu();
+    matched = (uint64_t)h[0].item<int64_t>();
+    zeros = (uint64_t)h[4].item<int64_t>();
+    TORCH_CHECK(h[1].item<int64_t>() == nR, "build_probe_group: the partitions hold ", h[1].item<int64_t>(),
+                " inner tuples, R has ", nR);
+  } else {
+    uint64_t n = 0;
+    matched = host::buildProbeGroup(a, reinterpret_cast<const uint64_t *>(vals), (uint64_t)ridOffset, stride,
+                                    ptr<uint32_t>(accCount), ptr<uint64_t>(accSum));
+    zeros = host::groupEmit(a, ptr<uint32_t>(accCount), sum ? ptr<uint64_t>(accSum) : nullptr, ptr<uint64_t>(rows),
+                            (uint64_t)nR, &n);
+    TORCH_CHECK((int64_t)n == nR, "build_probe_group: the partitions hold ", n, " inner tuples, R has ", nR);
+  }
+  py::dict d;
+  d["rows"] = rows;
+  d["counts"] = accCount.narrow(0, 0, nR).to(at::kLong);
+  d["sums"] = accSum.narrow(0, 0, nR);
+  d["matched_pairs"] = matched;
+  d["unmatched_inner"] = zeros;
+  return d;
+}
+
 at::Tensor opGenerate(int64_t n, int64_t globalOffset, int64_t globalSize, const data::GenSpec &spec,
                       const std::string &device) {
   at::Tensor out = at::empty({n, 2}, at::TensorOptions().dtype(at::kLong).device(device));
@@ -1234,6 +1344,7 @@ py::dict resultToDict(const operators::JoinResult &r) {
   d["global_matches"] = r.globalMatches;
   d["output_pairs"] = r.outputPairs;
   d["output_rids"] = r.outputRids;
+  d["output_groups"] = r.outputGroups;
   d["matched_pairs"] = r.matchedPairs;
   d["unmatched_inner"] = r.unmatchedInner;
   d["unmatched_outer"] = r.unmatchedOuter;
@@ -1299,6 +1410,24 @@ static py::dict statsToDict(const operators::LateMaterialization::Stats &st) {
   return d;
 }
 
+// kind = GROUP with materialize: the rows of the last run(), int64 [m, 2]
+// (inner rid, count) or [m, 3] (inner rid, count, sum), any order.
+static at::Tensor groupRows(operators::HashJoin &j) {
+  const auto &r = j.lastResult();
+  const int64_t n = (int64_t)r.outputGroups, W = r.groupSums ? 3 : 2;
+  at::Tensor out = at::empty({n, W}, at::kLong);
+  if (n && j.getOutputGroups()) {
+    HJ_CHECK(j.outputGroupsValid(),
+             "HashJoin.output_groups(): the rows of the last run were in the engine workspace, which a later join, "
+             "plan or trim_workspace on the same context has since reused; read output_groups() right after run()");
+    if (j.context()->onDevice())
+      HIP_CHECK(hipMemcpy(out.data_ptr(), j.getOutputGroups(), (size_t)n * W * 8, hipMemcpyDefault));
+    else
+      std::memcpy(out.data_ptr(), j.getOutputGroups(), (size_t)n * W * 8);
+  }
+  return out;
+}
+
 static void checkPayloadCover(const operators::HashJoin &j, const at::Tensor &a, uint64_t offA, const at::Tensor &b,
                               uint64_t offB) {
   const uint64_t off[2] = {offA, offB}, rows[2] = {(uint64_t)a.size(0), (uint64_t)b.size(0)};
@@ -1317,6 +1446,8 @@ static void checkKindRows(const operators::HashJoin &j, const char *entry, const
                           uint64_t innerOffset, const at::Tensor &outerRows, uint64_t outerOffset) {
   const core::JoinKind kind = j.getConfig().kind;
   const uint32_t world = j.context()->comm()->size();
+  TORCH_CHECK(kind != core::JoinKind::Group, entry, ": kind=GROUP has no payload rows: its result is one (rid, "
+              "count[, sum]) row per inner tuple (output_groups(), join_group)");
   TORCH_CHECK(world == 1, entry, ": payload rows of a kind=", core::joinKindName(kind),
               " join need a single rank, this join runs on ", world,
               " (a NULL rid has no owner to fetch a row from; rid lists are not exchanged)");
@@ -1419,7 +1550,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .value("ANTI", core::JoinKind::Anti)
       .value("LEFT_OUTER", core::JoinKind::LeftOuter)
       .value("RIGHT_OUTER", core::JoinKind::RightOuter)
-      .value("FULL_OUTER", core::JoinKind::FullOuter);
+      .value("FULL_OUTER", core::JoinKind::FullOuter)
+      .value("GROUP", core::JoinKind::Group);
   py::class_<core::JoinConfig>(m, "JoinConfig")
       .def(py::init<>())
       .def_readwrite("kind", &core::JoinConfig::kind)
@@ -1841,7 +1973,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
             TORCH_CHECK(j.getConfig().materialize, "join was not run with materialize=True");
             TORCH_CHECK(j.getConfig().kind == core::JoinKind::Inner,
                         "materialize_payloads needs kind=INNER: a kind=SEMI / ANTI join has outer rids "
-                        "(output_rids()), not pairs, and an outer kind has NULL rids without a row");
+                        "(output_rids()), not pairs, an outer kind has NULL rids without a row, and kind=GROUP "
+                        "has group rows (output_groups())");
             TORCH_CHECK(!j.lastResult().rowsFused, "the last run wrote rows directly (join_materialized)");
             TORCH_CHECK(innerRows.dim() == 2 && innerRows.size(1) == (int64_t)kernels::ROW_WORDS &&
                             outerRows.dim() == 2 && outerRows.size(1) == (int64_t)kernels::ROW_WORDS,
@@ -1878,7 +2011,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
             TORCH_CHECK(j.getConfig().materialize, "join_materialized needs materialize=True");
             TORCH_CHECK(j.getConfig().kind == core::JoinKind::Inner,
                         "join_materialized cannot be combined with kind=SEMI / ANTI / LEFT_OUTER / RIGHT_OUTER / "
-                        "FULL_OUTER: such a join has outer rids (output_rids()) or NULL rids without a row, not "
+                        "FULL_OUTER / GROUP: such a join has outer rids (output_rids()), NULL rids without a row, or "
+                        "one aggregate row per inner tuple (output_groups()), not "
                         "(inner, outer) pairs to fetch rows for");
             TORCH_CHECK(innerRows.dim() == 2 && innerRows.size(1) == (int64_t)kernels::ROW_WORDS &&
                             outerRows.dim() == 2 && outerRows.size(1) == (int64_t)kernels::ROW_WORDS,
@@ -2034,6 +2168,33 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         }
         return out;
       })
+      .def("output_groups", [](operators::HashJoin &j) { return groupRows(j); })
+      .def(
+          "join_group",
+          [](operators::HashJoin &j, std::shared_ptr<core::ExecContext> ctx, at::Tensor outerValues, uint64_t outerOffset,
+             uint64_t outerGlobal) {
+            // One kind=GROUP join that also sums outer_values per group: (result dict, rows [|R|, 3]).
+            // outer_values: 1-D int64, any positive element stride (a column view of a payload tensor).
+            TORCH_CHECK(j.getConfig().kind == core::JoinKind::Group, "join_group needs kind=GROUP, this join has kind=",
+                        core::joinKindName(j.getConfig().kind));
+            TORCH_CHECK(j.getConfig().materialize, "join_group needs materialize=True");
+            TORCH_CHECK(outerValues.dim() == 1 && outerValues.scalar_type() == at::kLong,
+                        "join_group: outer_values must be a 1-D int64 tensor");
+            TORCH_CHECK(outerValues.size(0) == 0 || outerValues.stride(0) >= 1,
+                        "join_group: outer_values need a positive element stride");
+            TORCH_CHECK(outerValues.is_cuda() == j.context()->onDevice(), "join_group: outer_values must live where the join runs");
+            TORCH_CHECK((uint64_t)outerValues.size(0) == outerGlobal, "join_group: outer_values has ", outerValues.size(0),
+                        " entries, outer_global says ", outerGlobal);
+            if (outerValues.is_cuda()) HIP_CHECK(hipDeviceSynchronize());  // values written on other streams
+            operators::JoinResult r;
+            {
+              py::gil_scoped_release nogil;
+              r = j.joinGroup(ptr<uint64_t>(outerValues), outerOffset, outerGlobal,
+                              outerValues.size(0) ? (uint64_t)outerValues.stride(0) : 1);
+            }
+            return py::make_tuple(resultToDict(r), groupRows(j));
+          },
+          py::arg("context"), py::arg("outer_values"), py::arg("outer_rid_offset") = 0, py::arg("outer_global_rows") = 0)
       .def("output_rids", [](operators::HashJoin &j) {
         // kind = SEMI / ANTI with materialize: the qualifying outer rids, int64 [m], any order.
         const uint64_t n = j.lastResult().outputRids;
@@ -2215,6 +2376,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   ops.def("build_probe_outer", &opBuildProbeOuter, py::arg("R"), py::arg("S"), py::arg("part_r"), py::arg("part_s"),
           py::arg("frag_shift"), py::arg("key_shift"), py::arg("wide") = false, py::arg("r_chunk") = 4096,
           py::arg("s_chunk") = 65536, py::arg("keep_inner") = true, py::arg("keep_outer") = true);
+  ops.def("build_probe_group", &opBuildProbeGroup, py::arg("R"), py::arg("S"), py::arg("part_r"), py::arg("part_s"),
+          py::arg("frag_shift"), py::arg("key_shift"), py::arg("wide") = false, py::arg("r_chunk") = 4096,
+          py::arg("s_chunk") = 65536, py::arg("values") = py::none(), py::arg("rid_offset") = 0);
   ops.def("generate", &opGenerate, py::arg("n"), py::arg("global_offset"), py::arg("global_size"), py::arg("spec"),
           py::arg("device") = "cpu");
   ops.def("scan_u32", &opScan);

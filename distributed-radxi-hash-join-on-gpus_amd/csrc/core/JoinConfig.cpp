@@ -2,6 +2,7 @@
 
 #include <algorithm>
 
+#include "../kernels/kernels.h"
 #include "../utils/Debug.h"
 
 namespace hpcjoin {
@@ -60,8 +61,10 @@ JoinPlan makePlan(const JoinConfig &cfg, uint32_t numberOfNodes, uint64_t global
   // fused row-output kernel, 3 workgroups per CU (kernels/build_probe.hip,
   // bpMatRowsKernel).  SF100: 35.6 ms fused vs 42.0 ms join + separate pass.
   // (Semi / anti joins keep keys only in LDS: sized as counting joins.  A
-  // materializing outer join runs the inner join's place pass: sized like it.)
-  const bool pairs = p.materialize && !isRidKind(p.kind);
+  // materializing outer join runs the inner join's place pass: sized like it.
+  // A group join forms no pairs: keys, counters and sums in LDS, sized below.)
+  const bool group = p.kind == JoinKind::Group;
+  const bool pairs = p.materialize && !isRidKind(p.kind) && !group;
   const bool matNarrow = pairs && !p.wide && !cfg.rChunk;
   const uint32_t matTarget = numberOfNodes == 1 ? 1024 : 2048;
   // >= 8 network partitions per node so LPT has room to balance.
@@ -108,6 +111,9 @@ JoinPlan makePlan(const JoinConfig &cfg, uint32_t numberOfNodes, uint64_t global
         p.keyOnly = true;
     }
   }
+  // Group joins: final partitions of one LDS table (rChunk below), so that no
+  // outer tuple is probed against several inner chunks.
+  if (group && !cfg.rChunk) splitBits(std::min<uint64_t>(cfg.buildTarget, p.wide ? 1024 : 2048));
   if (p.keyOnly) {
     // 8-byte table entries: final partitions of <= 2048 inner tuples give 36 KiB
     // LDS tables (4 workgroups per CU).  Measured on 1B x 1B sparse keys:
@@ -148,6 +154,13 @@ JoinPlan makePlan(const JoinConfig &cfg, uint32_t numberOfNodes, uint64_t global
   // (4 per CU); wide entries get 64 KiB (2 per CU).
   if (cfg.rChunk) {
     p.rChunk = cfg.rChunk;
+  } else if (group) {
+    // Keys, u32 counters and u64 sums per slot (kernels::bpGroup).  Whether a
+    // value column comes is known only at run time, so the table is sized with
+    // it: the largest rChunk whose table lets two workgroups share a CU (80
+    // KiB each): 2048 (64 KiB + 64 B; wide 80 KiB + 64 B -> 1024, 40 KiB).
+    p.rChunk = 4096;
+    while (p.rChunk > 64 && kernels::groupTableBytes(p.rChunk, p.wide, true) > 80 * 1024) p.rChunk /= 2;
   } else {
     const uint32_t entry = p.wide ? (pairs ? 16 : 8) : (pairs || p.keyOnly ? 8 : 4);
     const uint32_t budget = (entry == 4 || p.keyOnly) ? 32 * 1024 : matNarrow ? 16 * matTarget : 64 * 1024;

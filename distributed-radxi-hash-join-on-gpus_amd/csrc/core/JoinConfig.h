@@ -80,7 +80,16 @@ enum class ExchangeMode : int {
 //     local_matches / global_matches count the result rows (pairs plus
 //     unmatched preserved tuples); JoinResult::matchedPairs / unmatchedInner /
 //     unmatchedOuter split them (kernels/outer_join.hip).
-enum class JoinKind : int { Inner = 0, Semi = 1, Anti = 2, LeftOuter = 3, RightOuter = 4, FullOuter = 5 };
+//   Group: the join followed by an aggregate grouped by the build side.  One
+//     row per inner tuple, also those without a partner: (inner rid, count)
+//     where count is the number of outer tuples with its key, or (inner rid,
+//     count, sum) with an outer value column (HashJoin::joinGroup; int64, the
+//     sum wraps).  Copies of an inner key each get the key's full count and
+//     sum.  No pair is formed (kernels/group_join.hip).  local_matches /
+//     global_matches count the result rows (this rank's inner tuples);
+//     matchedPairs is the sum of the counts (the inner join's count),
+//     unmatchedInner the groups with count 0, unmatchedOuter 0.
+enum class JoinKind : int { Inner = 0, Semi = 1, Anti = 2, LeftOuter = 3, RightOuter = 4, FullOuter = 5, Group = 6 };
 inline const char *joinKindName(JoinKind k) {
   switch (k) {
     case JoinKind::Semi: return "semi";
@@ -88,6 +97,7 @@ inline const char *joinKindName(JoinKind k) {
     case JoinKind::LeftOuter: return "left";
     case JoinKind::RightOuter: return "right";
     case JoinKind::FullOuter: return "full";
+    case JoinKind::Group: return "group";
     default: return "inner";
   }
 }
@@ -103,7 +113,9 @@ struct JoinConfig {
   // the output is the NULL-padded pair list (HashJoin::getOutput); refused when
   // a rid equals NULL_RID.  No kind but Inner is combined with outputHost, a
   // RowSink (HashJoin::setRowSink; their payload rows go through
-  // setKindRowSink at N = 1), or a materializing capacity spill.
+  // setKindRowSink at N = 1), or a materializing capacity spill.  Group: with
+  // materialize the output is the group rows (HashJoin::getOutputGroups); it
+  // takes no row sink of either sort.
   JoinKind kind = JoinKind::Inner;
   uint32_t networkBits = 0;   // radix bits of the network pass (0 = auto)
   uint32_t localBits = 0;     // radix bits of the local pass (0 = auto; ignored if !twoLevel)

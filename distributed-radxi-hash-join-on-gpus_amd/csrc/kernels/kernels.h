@@ -451,6 +451,14 @@ struct RowSink {
   uint64_t *out = nullptr;  // [capacity][10] u64
   uint64_t capacity = 0;
 };
+// Outer value column of a group join with a sum (HashJoin::setGroupValues):
+// the value of rid r is values[(r - offset) * strideWords], rids [offset, offset + rows).
+struct GroupValues {
+  const uint64_t *values = nullptr;
+  uint64_t offset = 0;
+  uint64_t rows = 0;
+  uint64_t strideWords = 1;
+};
 size_t bpLdsBytes(const BPArgs &a);
 // True when a count over the split layout uses the direct-addressed count
 // table (fragments <= 13 bits): its LDS table does not grow with the inner
@@ -556,6 +564,45 @@ void markPlacePairs(const BPArgs &a, const MarkUnit *units, const uint32_t *nUni
                     const unsigned long long *marks, const unsigned long long *unitOffsets,
                     const unsigned long long *base0, const unsigned long long *base1, bool innerSide, ulonglong2 *out,
                     uint64_t outCapacity, hipStream_t s);
+
+// Group joins (group_join.hip; core::JoinKind::Group): per inner tuple the
+// number of outer tuples with its key and, with a value column, the int64 sum
+// (wrapping) of values[(rid - ridOffset) * strideWords] over those tuples.
+// Slots of the largest hashed table of a launch, and its LDS bytes: 4- or
+// 8-byte keys, a u32 counter and (sum) a u64 accumulator per slot, plus the
+// reduction words.  Inline: the planner sizes rChunk with it (core::makePlan).
+HJ_HD uint64_t groupMaxSlots(uint32_t rChunk) {
+  uint32_t b = 6;
+  while ((uint64_t(1) << b) < 2ull * rChunk) ++b;
+  return uint64_t(1) << b;
+}
+HJ_HD size_t groupTableBytes(uint32_t rChunk, bool wide, bool sum) {
+  return (size_t)(groupMaxSlots(rChunk) * ((wide ? 8 : 4) + 4 + (sum ? 8 : 0)) + 64);
+}
+// The LDS request of bpGroup (direct-addressed counts when there is no value
+// column and the fragments have at most 13 bits; the hashed table otherwise).
+size_t bpGroupLdsBytes(const BPArgs &a, bool sum);
+// Over the BPItem list of bpPlanCounts / bpEmit.  accCount (u32) and accSum
+// (u64, only read with values) are indexed by the position in the partitioned
+// inner buffer and zeroed by the caller; every item adds its outer chunk's
+// count and sum of each inner tuple's key (global atomics), and the pairs
+// (the sum of all counts) to *a.result.  values == null: counts only, reads
+// no rid.  The caller guarantees fewer than 2^32 outer tuples per key.
+// Layouts: CompressedTuples, split columns, wide tuples (not key-only words).
+void bpGroup(const BPArgs &a, const BPItem *items, const uint32_t *nItems, uint32_t capacity,
+             const unsigned long long *values, uint64_t ridOffset, uint64_t strideWords, uint32_t *accCount,
+             unsigned long long *accSum, hipStream_t s);
+// Over the units of a.S (the inner side: outerSwapSides): unitCounts[u] = the
+// unit's length (every position is a group).
+void groupUnitLengths(const BPArgs &a, const MarkUnit *units, const uint32_t *nUnits, uint32_t capacity,
+                      uint32_t *unitCounts, hipStream_t s);
+// Rows (rid, count) -- with accSum (rid, count, sum) -- of unit u's positions,
+// in position order from out[unitOffsets[u] * W] (W = 2 or 3 words; rows at or
+// beyond outCapacity are not stored); the groups with count 0 are added to
+// *a.result.  out == null: only counts them.
+void groupEmit(const BPArgs &a, const MarkUnit *units, const uint32_t *nUnits, uint32_t capacity,
+               const uint32_t *accCount, const unsigned long long *accSum, const unsigned long long *unitOffsets,
+               unsigned long long *out, uint64_t outCapacity, hipStream_t s);
 
 // Single-level counting join of unique inner keys (bitmap_join.hip): one
 // workgroup per network partition sets a 2^bits LDS bitmap from the inner
@@ -904,6 +951,7 @@ void preloadBuildProbe();
 void preloadKeyTables();
 void preloadSemiJoin();
 void preloadOuterJoin();
+void preloadGroupJoin();
 void preloadBitmapJoin();
 void preloadScan();
 void preloadWire();
@@ -919,6 +967,7 @@ inline void preloadCodeObjects() {
   preloadKeyTables();
   preloadSemiJoin();
   preloadOuterJoin();
+  preloadGroupJoin();
   preloadBitmapJoin();
   preloadScan();
   preloadWire();

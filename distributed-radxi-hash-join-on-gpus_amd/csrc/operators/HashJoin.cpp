@@ -127,7 +127,7 @@ void HashJoin::planPasses() {
   if (K == 1) return;
   JOIN_ASSERT(!plan.materialize || plan.kind == core::JoinKind::Inner, "HashJoin",
               "capacity spill (%u passes) of a materializing JoinConfig.kind = %s join is not supported: its rid or row "
-              "list lives in the workspace; count-only semi-, anti- and outer joins do spill",
+              "list lives in the workspace; count-only semi-, anti-, outer and group joins do spill",
               K, core::joinKindName(plan.kind));
   JOIN_ASSERT(!plan.materialize || config.outputHost, "HashJoin",
               "capacity spill (%u passes) of a materializing join needs JoinConfig.outputHost: the pairs of every "
@@ -287,6 +287,7 @@ JoinResult HashJoin::runPasses() {
   total.networkMs = total.joinMs;
   result = total;
   outputRids = nullptr;  // count-only: the pass joins' rid lists (if any) are gone with their workspace
+  outputGroups = nullptr;
   if (plan.materialize) {  // every pass appended to the caller's host buffer
     output = static_cast<const ulonglong2 *>(config.outputHost);
     outputEpoch = ctx->workspace().epoch();
@@ -305,7 +306,8 @@ void HashJoin::makeJoinPlan() {
               "relations must live where the engine runs (%s) or in pinned host memory", locationName(ctx->location()));
   JOIN_ASSERT(config.kind == core::JoinKind::Inner || !config.outputHost, "HashJoin",
               "JoinConfig.kind = %s cannot be combined with JoinConfig.outputHost (output_host): a semi- or anti-join "
-              "writes outer rids, and an outer join its NULL-padded rows, to the workspace, not pairs to a host buffer",
+              "writes outer rids, an outer join its NULL-padded rows and a group join its group rows to the workspace, "
+              "not pairs to a host buffer",
               core::joinKindName(config.kind));
   // Max key / rid over both relations and all ranks (the plan must be identical
   // everywhere), plus each rank's rid range per relation and exchange chunk
@@ -381,6 +383,11 @@ void HashJoin::makeJoinPlan() {
                         mx[1]);
   planMaxKey = mx[0];
   planMaxRid = mx[1];
+  // Group joins count in u32 accumulators per inner tuple: a key cannot have 2^32 outer partners.
+  JOIN_ASSERT(config.kind != core::JoinKind::Group || outerRelation->getGlobalSize() < (1ull << 32), "HashJoin",
+              "JoinConfig.kind = group: %lu outer tuples; the per-group counters are 32 bits wide (fewer than 2^32 "
+              "outer tuples)",
+              (unsigned long)outerRelation->getGlobalSize());
   JOIN_ASSERT(!core::isOuterKind(config.kind) || planMaxRid != kernels::NULL_RID, "HashJoin",
               "JoinConfig.kind = %s: a rid equals NULL_RID (0xFFFFFFFFFFFFFFFF), which pads the unmatched rows",
               core::joinKindName(config.kind));
@@ -578,6 +585,19 @@ std::vector<uint64_t> HashJoin::workspaceParts() const {
   // Build/probe work lists (items or spans, 32 B) and materialized pairs.
   parts[0] += (2 * P + recvTotal[1] / std::max<uint32_t>(plan.sChunk, 1) +
                recvTotal[0] / std::max<uint32_t>(plan.rChunk, 1) + 2048) * 48;
+  if (plan.kind == core::JoinKind::Group) {
+    // Count and sum accumulators (u32 + u64 per slot of the inner local pass
+    // output), the inner unit arrays and, materializing, three words per
+    // inner tuple of the window (tasks/BuildProbe, executeGroup).
+    const uint64_t slots = plan.twoLevel ? kernels::localSampledCapacityBound(
+                                               recvTotal[0], P, std::max<uint32_t>(1, plan.localSampleStride), 64)
+                                         : recvTotal[0];
+    const uint64_t units = P + recvTotal[0] / kernels::MARK_UNIT + 2;
+    parts[0] += units * (sizeof(kernels::MarkUnit) + 4 + 8) + kernels::scanWorkspaceBytes(units) + 4096;
+    parts.push_back((slots + 2) * 12);
+    if (plan.materialize) parts.push_back((recvTotal[0] + 1) * 24);
+    return parts;
+  }
   if (core::isOuterKind(plan.kind)) {
     // Marks and unit arrays (list, counts, 64-bit offsets) per preserved side,
     // per-item pair counts and offsets, and the row buffer at its default
@@ -788,6 +808,41 @@ bool HashJoin::lowKeyBitsSkewed() {
 
 bool HashJoin::outputValid() const { return output && ctx->workspace().epoch() == outputEpoch; }
 bool HashJoin::outputRidsValid() const { return outputRids && ctx->workspace().epoch() == outputEpoch; }
+bool HashJoin::outputGroupsValid() const { return outputGroups && ctx->workspace().epoch() == outputEpoch; }
+
+void HashJoin::setGroupValues(const kernels::GroupValues &v) {
+  JOIN_ASSERT(plan.kind == core::JoinKind::Group, "HashJoin",
+              "a value column to sum (join_group) needs JoinConfig.kind = group, this join has kind = %s",
+              core::joinKindName(plan.kind));
+  JOIN_ASSERT(ctx->comm()->size() == 1, "HashJoin",
+              "join_group: a value column of a kind = group join needs a single rank (world size %u): the values of "
+              "outer tuples received from other ranks live on those ranks; without a value column every rank counts",
+              ctx->comm()->size());
+  JOIN_ASSERT(passes == 1, "HashJoin", "join_group: a value column cannot be combined with a capacity spill (%u passes)",
+              passes);
+  JOIN_ASSERT(v.values && v.strideWords >= 1, "HashJoin", "join_group: needs a value column with a positive stride");
+  JOIN_ASSERT(ridLo[1] > ridHi[1] || (ridLo[1] >= v.offset && ridHi[1] - v.offset < v.rows), "HashJoin",
+              "join_group: outer values [%lu, %lu) do not cover this rank's outer rids [%lu, %lu]",
+              (unsigned long)v.offset, (unsigned long)(v.offset + v.rows), (unsigned long)ridLo[1],
+              (unsigned long)ridHi[1]);
+  groupValues = v;
+  hasGroupValues = true;
+}
+
+JoinResult HashJoin::joinGroup(const uint64_t *outerValues, uint64_t outerOffset, uint64_t outerGlobal,
+                               uint64_t strideWords) {
+  kernels::GroupValues v;
+  v.values = outerValues;
+  v.offset = outerOffset;
+  v.rows = outerGlobal;
+  v.strideWords = strideWords;
+  setGroupValues(v);
+  struct Clear {
+    HashJoin &j;
+    ~Clear() { j.clearGroupValues(); }
+  } clear{*this};
+  return run();
+}
 
 void HashJoin::join() {
   run();
@@ -797,7 +852,8 @@ void HashJoin::join() {
 void HashJoin::setRowSink(const kernels::RowSink &s) {
   JOIN_ASSERT(plan.kind == core::JoinKind::Inner, "HashJoin",
               "JoinConfig.kind = %s cannot be combined with a RowSink (join_materialized): a semi- or anti-join has "
-              "outer rids, and an outer join NULL rids without a row, not (inner, outer) pairs to fetch rows for",
+              "outer rids, an outer join NULL rids without a row, and a group join one aggregate row per inner tuple, "
+              "not (inner, outer) pairs to fetch rows for",
               core::joinKindName(plan.kind));
   const uint64_t off[2] = {s.offA, s.offB}, rows[2] = {s.rowsAN, s.rowsBN};
   for (int r = 0; r < 2; ++r)
@@ -826,6 +882,9 @@ bool HashJoin::canFuseKindRows() const {
 void HashJoin::setKindRowSink(const kernels::RowSink &s) {
   JOIN_ASSERT(plan.kind != core::JoinKind::Inner, "HashJoin",
               "setKindRowSink is the row sink of semi, anti and outer joins; kind = inner takes setRowSink");
+  JOIN_ASSERT(plan.kind != core::JoinKind::Group, "HashJoin",
+              "join_rows / materialize_rows: JoinConfig.kind = group has no payload rows: its result is one (rid, "
+              "count[, sum]) row per inner tuple (output_groups(), join_group)");
   JOIN_ASSERT(ctx->comm()->size() == 1, "HashJoin",
               "join_rows: payload rows of a kind = %s join need a single rank (world size %u): a NULL rid has no "
               "owner to fetch a row from",
@@ -883,6 +942,7 @@ JoinResult HashJoin::runImpl() {
     if (bitmap.run(run.t0, result)) {
       output = nullptr;
       outputRids = bitmap.outputRids();  // set plan, materializing; null otherwise
+      outputGroups = nullptr;
       outputEpoch = ctx->workspace().epoch();
       RESULT_COUNTER = result.localMatches;
       return result;
@@ -942,11 +1002,13 @@ JoinResult HashJoin::runImpl() {
 
   // --------------------------------------------- local pass and build/probe
   LocalPhase local(env, localOverflowed, hasSink && (canFuseRows() || canFuseKindRows()) ? &sink : nullptr);
+  if (hasGroupValues && plan.kind == core::JoinKind::Group) local.setGroupValues(&groupValues);
   local.run(run, result);
   const uint64_t t4 = nowUs();
   ctx->timeline().resolve();  // every stream was synchronised above
   output = local.buildProbes().empty() ? nullptr : local.buildProbes().front()->getOutput();
   outputRids = local.buildProbes().empty() ? nullptr : local.buildProbes().front()->getOutputRids();
+  outputGroups = local.buildProbes().empty() ? nullptr : local.buildProbes().front()->getOutputGroups();
   outputEpoch = ctx->workspace().epoch();
   local.release();
   result.wireBytes = run.inner->wireBytesSent() + run.outer->wireBytesSent();

@@ -38,7 +38,11 @@ struct JoinResult {
   // Outer kinds, local to the rank: localMatches = matchedPairs + unmatchedInner
   // + unmatchedOuter (the result rows); an unmatched count is 0 for a side
   // that is not preserved.  With materialize, outputPairs rows are written.
+  // Kind Group: localMatches = the result rows (this rank's inner tuples),
+  // matchedPairs the sum of their counts, unmatchedInner the rows with count 0.
   uint64_t matchedPairs = 0, unmatchedInner = 0, unmatchedOuter = 0;
+  uint64_t outputGroups = 0;       // kind Group, materialize: rows written on this rank
+  bool groupSums = false;          // kind Group: the rows carry a sum (3 words, else 2)
   bool rowsFused = false;          // materialize: whole rows went to the RowSink (no pair array)
   uint32_t reruns = 0;             // build/probe re-launches after an item/output overflow
   double joinMs = 0;               // host wall: histogram start -> local result available
@@ -107,6 +111,18 @@ class HashJoin {
   // under the same validity rule as getOutput().
   const uint64_t *getOutputRids() const { return outputRids; }
   bool outputRidsValid() const;
+  // kind Group with materialize: the rows of the last run()
+  // (lastResult().outputGroups of them, any order; 2 words (rid, count) or,
+  // when it summed a value column, 3 words (rid, count, sum)), in the engine's
+  // workspace under the same validity rule as getOutput().
+  const uint64_t *getOutputGroups() const { return outputGroups; }
+  bool outputGroupsValid() const;
+  // kind Group: while set, run() also sums the outer value column per group
+  // (N = 1: the values of other ranks' outer tuples are not here).  Throws
+  // unless the column covers this rank's outer rids.  joinGroup = set, run, clear.
+  void setGroupValues(const kernels::GroupValues &v);
+  void clearGroupValues() { hasGroupValues = false; }
+  JoinResult joinGroup(const uint64_t *outerValues, uint64_t outerOffset, uint64_t outerGlobal, uint64_t strideWords);
   // Fused materialization: while a sink is set, a device join at N = 1 over
   // the split layout writes whole output rows (LateMaterialization's layout)
   // from its materialize pass instead of pairs.  canFuseRows() says whether
@@ -191,6 +207,9 @@ class HashJoin {
   bool bitmapExact = false;        // bitmap plan: exact histograms (small inputs, or after an overflow)
   const ulonglong2 *output = nullptr;
   const uint64_t *outputRids = nullptr;
+  const uint64_t *outputGroups = nullptr;
+  kernels::GroupValues groupValues;
+  bool hasGroupValues = false;
   // Capacity spill (planPasses / runPasses): pass count, this rank's and the
   // global tuple counts per pass, the pass buffers (one inner and one outer
   // pass at a time) and the plan's global key / rid bounds.

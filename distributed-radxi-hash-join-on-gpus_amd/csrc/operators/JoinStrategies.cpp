@@ -197,6 +197,7 @@ bool ExactExchange::exchange(JoinRun &run) {
 tasks::BuildProbe *LocalPhase::addBuildProbe(data::Window *inner, data::Window *outer) {
   bps.emplace_back(new tasks::BuildProbe(inner, outer, env.ctx, env.plan, env.config.outputCapacity));
   if (sink) bps.back()->setRowSink(sink);
+  if (groupValues) bps.back()->setGroupValues(groupValues->values, groupValues->offset, groupValues->strideWords);
   if (env.config.outputHost && env.plan.materialize) {
     JOIN_ASSERT(env.config.outputCapacity > 0, "HashJoin", "outputHost needs outputCapacity (pairs it holds)");
     bps.back()->setHostOutput(env.config.outputHost);
@@ -288,9 +289,12 @@ void LocalPhase::run(JoinRun &run, JoinResult &r) {
   }
   // Materializing joins have exactly one build/probe (never pipelined).
   const bool rids = core::isRidKind(env.plan.kind);  // semi / anti: outer rids; inner and outer kinds: pairs
-  r.outputPairs = env.plan.materialize && !rids && !bps.empty() ? bps.front()->getOutputCount() : 0;
+  const bool group = env.plan.kind == core::JoinKind::Group;  // rows (rid, count[, sum])
+  r.outputPairs = env.plan.materialize && !rids && !group && !bps.empty() ? bps.front()->getOutputCount() : 0;
   r.outputRids = env.plan.materialize && rids && !bps.empty() ? bps.front()->getOutputCount() : 0;
-  if (core::isOuterKind(env.plan.kind) && !bps.empty()) {  // (never pipelined: one build/probe)
+  r.outputGroups = env.plan.materialize && group && !bps.empty() ? bps.front()->getOutputCount() : 0;
+  r.groupSums = group && groupValues;
+  if ((core::isOuterKind(env.plan.kind) || group) && !bps.empty()) {  // (never pipelined: one build/probe)
     r.matchedPairs = bps.front()->getMatchedPairs();
     r.unmatchedInner = bps.front()->getUnmatchedInner();
     r.unmatchedOuter = bps.front()->getUnmatchedOuter();

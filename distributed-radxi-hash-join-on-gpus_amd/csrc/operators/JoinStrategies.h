@@ -131,6 +131,8 @@ class LocalPhase {
   // Runs to completion (all streams synchronised); fills the counts of `r`.
   void run(JoinRun &run, JoinResult &r);
   std::vector<std::unique_ptr<tasks::BuildProbe>> &buildProbes() { return bps; }
+  // kind Group: the outer value column to sum (null: counts only).
+  void setGroupValues(const kernels::GroupValues *v) { groupValues = v; }
   void release() {
     bps.clear();
     outerViews.clear();
@@ -141,6 +143,7 @@ class LocalPhase {
   JoinEnv &env;
   bool &localOverflowed;
   const kernels::RowSink *sink;  // fused row output (N = 1 materializing joins), or null
+  const kernels::GroupValues *groupValues = nullptr;
   std::vector<std::unique_ptr<tasks::BuildProbe>> bps;
   std::vector<std::unique_ptr<data::Window>> outerViews;
 };

@@ -363,6 +363,96 @@ void BuildProbe::executeOuter() {
   readBackCounters();
 }
 
+// Group join (kernels/group_join.hip): no pair is written and nothing can
+// overflow but the item list -- the rows are this rank's inner tuples.  The
+// accumulators (u32 counts, u64 sums over the positions of the partitioned
+// inner buffer) and the unit counts are zeroed here, so every re-run (item-list
+// overflow in collect(), the exact redo after a sampled local pass overflowed,
+// a second run()) starts clean.
+void BuildProbe::executeGroup() {
+  const bool dev = ctx->onDevice();
+  const bool sum = groupValues != nullptr;
+  const uint64_t W = sum ? 3 : 2;
+  memory::Arena &ws = ctx->workspace();
+  performance::Timeline &tl = ctx->timeline();
+  const double wb = (double)innerPartitionSize, wp = (double)outerPartitionSize;
+  performance::Measurements::add("BPBUILDELEM", wb, "tuples");
+  performance::Measurements::add("BPPROBEELEM", wp, "tuples");
+  args.materialize = false;  // no pairs; plan.materialize asks for the rows
+  const uint64_t slots = (windows[0]->getPartitionedCapacity() + 2) & ~1ull;  // (u32 counts zeroed as whole words)
+  uint32_t *accCount = ws.getArray<uint32_t>(slots);
+  auto *accSum = sum ? ws.getArray<unsigned long long>(slots) : nullptr;
+  ctx->zero(accCount, slots * sizeof(uint32_t));
+  if (sum) ctx->zero(accSum, slots * sizeof(unsigned long long));
+  outputCapacity = innerPartitionSize;  // one row per inner tuple: cannot overflow
+  outGroups = plan.materialize ? ws.getArray<uint64_t>(std::max<uint64_t>(1, outputCapacity * W)) : nullptr;
+  if (!dev) {
+    tl.begin("BPTASKTIME");
+    tl.beginSplit("BPKERNEL", "BPBUILD", wb, "BPPROBE", wp);
+    uint64_t rows = 0;
+    matchedPairs = host::buildProbeGroup(args, groupValues, groupOffset, groupStride, accCount,
+                                         reinterpret_cast<uint64_t *>(accSum));
+    unmatchedInner = host::groupEmit(args, accCount, reinterpret_cast<const uint64_t *>(accSum), outGroups,
+                                     outputCapacity, &rows);
+    tl.end("BPKERNEL");
+    tl.end("BPTASKTIME");
+    unmatchedOuter = 0;
+    matches = rows;
+    outputCount = plan.materialize ? rows : 0;
+    workItems = args.P;
+    return;
+  }
+  tl.begin("BPTASKTIME", ctx->stream());
+  const uint64_t tAlloc = performance::nowUs();
+  const uint32_t P1 = std::max<uint32_t>(args.P, 1);
+  // Units of the inner side (also of partitions without outer tuples, which get no work item).
+  kernels::BPArgs uargs = kernels::outerSwapSides(args, kernels::MARK_UNIT);
+  unitCapacityR = (uint32_t)std::min<uint64_t>(0xFFFFFFF0ull,
+                                               ((uint64_t)args.P + innerPartitionSize / uargs.sChunk + 2) & ~1ull);
+  counters = ws.getArray<unsigned long long>(kCounters);
+  ctx->zero(counters, kCounters * sizeof(unsigned long long));
+  args.result = counters;       // [0] pairs
+  uargs.result = counters + 4;  // [4] empty groups
+  uint32_t *nItems = reinterpret_cast<uint32_t *>(counters + 2);
+  uint32_t *nUnits = reinterpret_cast<uint32_t *>(counters + 6);
+  uint32_t *counts = ws.getArray<uint32_t>(P1);
+  uint32_t *offsets = ws.getArray<uint32_t>(P1);
+  void *scanWs = ws.get(kernels::scanWorkspaceBytes(std::max<uint64_t>(args.P, unitCapacityR)));
+  kernels::BPItem *items = ws.getArray<kernels::BPItem>(capacity);
+  auto *units = ws.getArray<kernels::MarkUnit>(unitCapacityR);
+  uint32_t *unitCounts = plan.materialize ? ws.getArray<uint32_t>(unitCapacityR) : nullptr;
+  unsigned long long *unitOffsets = plan.materialize ? ws.getArray<unsigned long long>(unitCapacityR) : nullptr;
+  performance::Measurements::add("BPMEMALLOC", (double)(performance::nowUs() - tAlloc), "us");
+  performance::Measurements::add("BPMEMSIZE",
+                                 (double)(2ull * P1 * 4 + kernels::scanWorkspaceBytes(std::max<uint64_t>(args.P, unitCapacityR)) +
+                                          (uint64_t)capacity * sizeof(kernels::BPItem) + slots * (sum ? 12 : 4) +
+                                          (uint64_t)unitCapacityR * (sizeof(kernels::MarkUnit) + 12) +
+                                          kernels::bpGroupLdsBytes(args, sum)),
+                                 "bytes");
+  hipStream_t s = ctx->stream();
+  kernels::bpPlanCounts(args, counts, s);
+  kernels::scanExclusiveU32(counts, offsets, args.P, nItems, scanWs, s);
+  kernels::bpEmit(args, counts, offsets, items, capacity, s);
+  if (unitCounts) ctx->zero(unitCounts, (uint64_t)unitCapacityR * sizeof(uint32_t));
+  tl.beginSplit("BPKERNEL", "BPBUILD", wb, "BPPROBE", wp, s);
+  kernels::bpGroup(args, items, nItems, capacity, reinterpret_cast<const unsigned long long *>(groupValues), groupOffset,
+                   groupStride, accCount, accSum, s);  // -> counters[0], accumulators
+  // Inner units (counts / offsets are free again: bpEmit has consumed them in stream order).
+  kernels::markPlanUnits(uargs, counts, s);
+  kernels::scanExclusiveU32(counts, offsets, args.P, nUnits, scanWs, s);
+  kernels::markEmitUnits(uargs, counts, offsets, units, unitCapacityR, s);
+  if (plan.materialize) {
+    kernels::groupUnitLengths(uargs, units, nUnits, unitCapacityR, unitCounts, s);
+    kernels::scanExclusiveU32to64(unitCounts, unitOffsets, unitCapacityR, counters + 1, scanWs, s);  // -> [1] rows
+  }
+  kernels::groupEmit(uargs, units, nUnits, unitCapacityR, accCount, accSum, unitOffsets,
+                     reinterpret_cast<unsigned long long *>(outGroups), outputCapacity, s);  // -> counters[4], rows
+  hipEvent_t done = tl.mark(s);
+  tl.endAt("BPKERNEL", done);
+  tl.endAt("BPTASKTIME", done);
+  readBackCounters();
+}
+
 void BuildProbe::execute() {
   if (reference) {
     args.result = nullptr;
@@ -371,6 +461,10 @@ void BuildProbe::execute() {
     return;
   }
   configure();
+  if (plan.kind == core::JoinKind::Group) {
+    executeGroup();
+    return;
+  }
   if (core::isOuterKind(plan.kind)) {
     executeOuter();
     return;
@@ -544,6 +638,26 @@ bool BuildProbe::collect() {
   std::memcpy(h, countersBack, sizeof(h));
   matches = h[0];
   outputCount = h[1];
+  if (plan.kind == core::JoinKind::Group) {
+    // [0] pairs [1] rows by the unit scan [2] item count (u32) [4] empty groups [6] inner unit count (u32)
+    uint32_t nItems, nUnits;
+    std::memcpy(&nItems, &h[2], sizeof(nItems));
+    std::memcpy(&nUnits, &h[6], sizeof(nUnits));
+    workItems = nItems;
+    matchedPairs = h[0];
+    unmatchedInner = h[4];
+    unmatchedOuter = 0;
+    matches = innerPartitionSize;  // one row per inner tuple of this rank's partitions
+    outputCount = plan.materialize ? matches : 0;
+    JOIN_ASSERT(nUnits <= unitCapacityR, "BuildProbe", "%u inner units, bound %u", nUnits, unitCapacityR);
+    if (nItems > capacity) {  // the only re-run: the rows cannot overflow
+      capacity = nItems;
+      return true;
+    }
+    JOIN_ASSERT(!plan.materialize || h[1] == matches, "BuildProbe", "group join: the units hold %lu rows, the window %lu",
+                (unsigned long)h[1], (unsigned long)matches);
+    return false;
+  }
   if (core::isOuterKind(plan.kind)) {
     // [0] pairs [1] pairs by the scan [2] item count (u32) [4] unmatched inner [5] unmatched outer
     // [6] inner / outer unit counts (u32 each)

@@ -11,6 +11,10 @@
 // the hit marks of the preserved sides) -> markCount(anti) over the units of
 // each preserved side -> (materialize) scans -> the inner join's place pass
 // -> markPlacePairs appends the NULL-padded rows (kernels/outer_join.hip).
+// Group joins: the same item list -> bpGroup (per-slot counters and sums in
+// LDS, added to accumulators over the inner positions) -> the inner side's
+// units -> (materialize) lengths, scan -> groupEmit writes the rows and counts
+// the empty groups (kernels/group_join.hip).
 // With a row sink (HashJoin::setKindRowSink, device, N = 1) the place pass of
 // those kinds writes payload rows instead: markPlaceRows in place of markPlace
 // / markPlacePairs, and for outer kinds over the split layout the inner join's
@@ -61,6 +65,16 @@ class BuildProbe : public Task {
   const ulonglong2 *getOutput() const { return outPairs; }
   // kind != Inner, materialize: getOutputCount() outer rids (null otherwise).
   const uint64_t *getOutputRids() const { return outRids; }
+  // kind Group, materialize: getOutputCount() rows of 2 (rid, count) or, with
+  // a value column, 3 (rid, count, sum) words (null otherwise).
+  const uint64_t *getOutputGroups() const { return outGroups; }
+  // kind Group: sum values[(rid - offset) * strideWords] over each group's
+  // outer tuples (the column covers this rank's outer rids; null = counts only).
+  void setGroupValues(const uint64_t *values, uint64_t offset, uint64_t strideWords) {
+    groupValues = values;
+    groupOffset = offset;
+    groupStride = strideWords;
+  }
   bool outputOverflowed() const { return overflowOut; }
   // Fused row output (device, split layout): the materialize pass writes whole
   // rows to the sink.  A sink overflow is reported, not re-run (the caller
@@ -86,6 +100,7 @@ class BuildProbe : public Task {
   void configure();
   void executeMarks();
   void executeOuter();
+  void executeGroup();
   core::ExecContext *ctx = nullptr;
   core::JoinPlan plan;
   data::Window *windows[2] = {nullptr, nullptr};
@@ -97,10 +112,14 @@ class BuildProbe : public Task {
   // semi / anti: [0] qualifying outer tuples [1] rids placed [2] item count (u32) [3] outer unit count (u32)
   // outer kinds: [0] pairs [1] pairs by the item-count scan [2] item count (u32) [3] place-pass matches (unused)
   // [4] unmatched inner [5] unmatched outer [6] inner / outer unit counts (u32 each) [7] spare
+  // group: [0] pairs [1] rows by the unit scan [2] item count (u32) [4] empty groups [6] inner unit count (u32)
   unsigned long long *counters = nullptr;
   unsigned long long *countersBack = nullptr;  // pinned copy, enqueued at the end of execute()
   ulonglong2 *outPairs = nullptr;
   uint64_t *outRids = nullptr;               // semi / anti: outer rid list (workspace)
+  uint64_t *outGroups = nullptr;             // group: rows (workspace)
+  const uint64_t *groupValues = nullptr;     // group: outer value column (null = counts only)
+  uint64_t groupOffset = 0, groupStride = 1;
   uint32_t unitCapacity = 0;                 // semi / anti / outer kinds: upper bound of the outer units
   uint32_t unitCapacityR = 0;                // outer kinds preserving R: upper bound of the inner units
   uint64_t matchedPairs = 0, unmatchedInner = 0, unmatchedOuter = 0;  // outer kinds (matches = their sum)

@@ -10,6 +10,7 @@ host twins (CPU tensors).  Tuples are int64 tensors of shape [n, 2] holding
     left_outer_join(R, S), right_outer_join(R, S), full_outer_join(R, S)   # pairs + NULL_RID-padded rows
     semi_join_rows(R, S, S_rows), anti_join_rows(R, S, S_rows)            # [m, 5]: outer rid + its payload row
     full_outer_join_rows(R, S, R_rows, S_rows)                            # [m, 10]: rids + both rows, NULL_RID-padded
+    group_join_count(R, S), group_join_sum(R, S, values)   # per inner tuple: [|R|, 2] (rid, count) / [|R|, 3] (+ sum)
 """
 from __future__ import annotations
 
@@ -91,6 +92,17 @@ def build_probe_mark_rows(R, S, part_r, part_s, frag_shift: int, key_shift: int,
     else; ``semi_count`` / ``anti_count`` are the full counts."""
     return _C().ops.build_probe_mark_rows(R, S, part_r, part_s, frag_shift, key_shift, wide, r_chunk, s_chunk,
                                           outer_rows, rid_offset, out_capacity)
+
+
+def build_probe_group(R, S, part_r, part_s, frag_shift: int, key_shift: int, wide=False, r_chunk=4096,
+                      s_chunk=65536, values=None, rid_offset=0) -> dict:
+    """Group join over matching partitions: ``rows`` (int64 ``[|R|, 2]`` of (inner rid, count), or ``[|R|, 3]``
+    of (inner rid, count, sum) with ``values``, a 1-D int64 tensor with ``values[rid - rid_offset]`` the value
+    of outer tuple ``rid``; any positive element stride), ``matched_pairs`` (the sum of the counts),
+    ``unmatched_inner`` (groups with count 0) and the raw accumulators ``counts`` / ``sums`` (int64, by position
+    of R)."""
+    return _C().ops.build_probe_group(R, S, part_r, part_s, frag_shift, key_shift, wide, r_chunk, s_chunk, values,
+                                      rid_offset)
 
 
 def build_probe_outer_rows(R, S, part_r, part_s, frag_shift: int, key_shift: int, wide=False, r_chunk=4096,
@@ -224,6 +236,38 @@ def right_outer_join_count(inner: torch.Tensor, outer: torch.Tensor, config=None
 def full_outer_join_count(inner: torch.Tensor, outer: torch.Tensor, config=None) -> int:
     """Rows of ``full_outer_join``."""
     return _outer_join(inner, outer, "FULL_OUTER", False, config)
+
+
+def _group_join(inner, outer, values, rid_offset: int, config=None) -> torch.Tensor:
+    C = _C()
+    cfg = config or C.JoinConfig()
+    cfg.kind = C.JoinKind.GROUP
+    cfg.materialize = True
+    on_dev = inner.is_cuda
+    ctx = C.ExecContext("device" if on_dev else "host", (inner.device.index or 0) if on_dev else -1,
+                        C.LocalCommunicator())
+    R = C.Relation.from_tensor(inner.contiguous(), inner.shape[0])
+    S = C.Relation.from_tensor(outer.contiguous(), outer.shape[0])
+    j = C.HashJoin(R, S, ctx, cfg)
+    if values is None:
+        j.run()
+        return j.output_groups()
+    _, rows = j.join_group(ctx, values, rid_offset, values.shape[0])
+    return rows
+
+
+def group_join_count(inner: torch.Tensor, outer: torch.Tensor, config=None) -> torch.Tensor:
+    """int64 [|inner|, 2]: ``(inner rid, count)`` per inner tuple, count = outer tuples with its key (0 for a
+    tuple without a partner; copies of a key each get the key's count); any order."""
+    return _group_join(inner, outer, None, 0, config)
+
+
+def group_join_sum(inner: torch.Tensor, outer: torch.Tensor, values: torch.Tensor, rid_offset: int = 0,
+                   config=None) -> torch.Tensor:
+    """int64 [|inner|, 3]: ``(inner rid, count, sum)`` per inner tuple, sum = the int64 (wrapping) sum of
+    ``values[rid - rid_offset]`` over the outer tuples with its key.  ``values`` is a 1-D int64 tensor of any
+    positive element stride (a column view such as ``S_rows[:, 2]`` is read in place)."""
+    return _group_join(inner, outer, values, rid_offset, config)
 
 
 def _kind_join_rows(inner, outer, kind: str, inner_rows, outer_rows, rid_offset: int, config=None) -> torch.Tensor:

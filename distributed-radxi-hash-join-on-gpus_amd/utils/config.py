@@ -31,6 +31,10 @@ def config_to_dict(cfg) -> dict:
     return d
 
 
+# Spellings of ``kind`` (dict value or HPCJOIN_KIND, any letter case): the names of JoinKind.
+KINDS = ("INNER", "SEMI", "ANTI", "LEFT_OUTER", "RIGHT_OUTER", "FULL_OUTER", "GROUP")
+
+
 def config_from_dict(d: dict | None = None, env_prefix: str = "HPCJOIN_"):
     """JoinConfig from a dict, overridden by HPCJOIN_<FIELD> environment variables."""
     C = require_native()

@@ -1,0 +1,175 @@
+#!/usr/bin/env python3
+"""Group joins (kind = GROUP) against what answers the same question without
+them, same relations, one process on one GPU.
+
+    python tools/bench_group.py [--workload gpu_128m] [--scale 1.0] [--steps 5] [--warmup 2]
+
+Runs the workload's Zipf-outer variant (theta 0.75 over the inner key domain)
+and prints one JSON line per configuration -- join_ms, the device build/probe
+span and (a only) the torch reduction as min / median / max over the timed
+iterations:
+
+  a  what a user does today: a materializing LEFT_OUTER join, then
+     torch.bincount over the inner rids of its pairs (count) and index_add_ of
+     the gathered value column (sum).  The pairs are brought to the device
+     outside the timed part; the torch part is timed with device events.
+  b  a count-only LEFT_OUTER join (bpOuterCount: the same key reads, marks in
+     place of counters).
+  c  a materializing GROUP join without a value column.
+  d  a materializing GROUP join with a value column (join_group).
+
+Every result is checked against oracle counts (sorted outer keys, searchsorted
+of the inner keys) and sums (wrapping prefix sums of the values in outer key
+order).  The last line compares the medians: c and d must lie below a by more
+than a's own min-to-max spread; c / b is reported.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def _spread(v):
+    return {"min": round(min(v), 3), "median": round(statistics.median(v), 3), "max": round(max(v), 3)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", default="gpu_128m")
+    ap.add_argument("--scale", type=float, default=1.0)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    a = ap.parse_args()
+    assert a.steps >= 5, "at least 5 timed steps per configuration"
+
+    import torch
+    import hpcjoin
+    from hpcjoin.models import workloads as W
+    C = hpcjoin.require_native()
+    assert torch.cuda.is_available(), "bench_group.py measures the device engine"
+    torch.cuda.set_device(0)
+    wl = W.get(a.workload, a.scale)
+    G_R, G_S = wl.inner_size, wl.outer_size
+    ctx = C.ExecContext("device", 0, C.LocalCommunicator())
+    inner = C.GenSpec(seed=1234)
+    outer = C.GenSpec(distribution=C.KeyDistribution.ZIPF, seed=4321, domain=G_R, zipf_theta=0.75)
+    R, S = C.Relation(G_R, G_R, "device", 0), C.Relation(G_S, G_S, "device", 0)
+    R.generate(inner, 0)
+    S.generate(outer, 0)
+    values = torch.randint(-2**40, 2**40, (G_S,), device="cuda", generator=torch.Generator("cuda").manual_seed(9))
+
+    # ---- oracle, by inner rid (rids are 0 .. G_R - 1)
+    Rt, St = R.to_tensor(), S.to_tensor()
+    sk, order = torch.sort(St[:, 0])
+    lo = torch.searchsorted(sk, Rt[:, 0].contiguous(), right=False)
+    hi = torch.searchsorted(sk, Rt[:, 0].contiguous(), right=True)
+    prefix = torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda"), torch.cumsum(values[St[:, 1][order]], 0)])
+    want_counts = torch.empty(G_R, dtype=torch.int64, device="cuda")
+    want_sums = torch.empty(G_R, dtype=torch.int64, device="cuda")
+    want_counts[Rt[:, 1]] = hi - lo
+    want_sums[Rt[:, 1]] = prefix[hi] - prefix[lo]  # int64 wraps both ways
+    pairs_total, empty = int(want_counts.sum()), int((want_counts == 0).sum())
+    del sk, order, lo, hi, prefix, Rt, St
+    torch.cuda.empty_cache()
+
+    def join(kind, materialize):
+        cfg = C.JoinConfig()
+        cfg.kind = getattr(C.JoinKind, kind)
+        cfg.materialize = materialize
+        return C.HashJoin(R, S, ctx, cfg)
+
+    def report(name, what, j, runs, extra=None):
+        line = {"workload": wl.name, "config": name, "what": what, "inner": G_R, "outer": G_S,
+                "join_ms": _spread([r["join_ms"] for r in runs]),
+                "dev_build_probe_ms": _spread([r["dev_build_probe_ms"] for r in runs]),
+                "matched_pairs": runs[-1]["matched_pairs"], "unmatched_inner": runs[-1]["unmatched_inner"],
+                "build_probe_items": runs[-1]["build_probe_items"], "reruns": runs[-1]["reruns"], "plan": repr(j.plan)}
+        line.update(extra or {})
+        print(json.dumps(line), flush=True)
+        return line
+
+    def by_rid(rows, col):
+        out = torch.empty(G_R, dtype=torch.int64, device="cuda")
+        out[rows[:, 0]] = rows[:, col]
+        return out
+
+    lines = {}
+    # ---- a: LEFT_OUTER pairs, then torch
+    j = join("LEFT_OUTER", True)
+    for _ in range(a.warmup):
+        j.run()
+    runs = [j.run() for _ in range(a.steps)]
+    pairs = j.output().cuda()
+    assert pairs.shape[0] == pairs_total + empty and runs[-1]["matched_pairs"] == pairs_total
+    torch_ms = {"count": [], "sum": []}
+    for it in range(a.warmup + a.steps):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record()
+        m = pairs[:, 1] != hpcjoin.NULL_RID
+        rid, srid = pairs[:, 0][m], pairs[:, 1][m]
+        counts = torch.bincount(rid, minlength=G_R)
+        ev[1].record()
+        sums = torch.zeros(G_R, dtype=torch.int64, device="cuda").index_add_(0, rid, values[srid])
+        ev[2].record()
+        torch.cuda.synchronize()
+        if it >= a.warmup:
+            torch_ms["count"].append(ev[0].elapsed_time(ev[1]))
+            torch_ms["sum"].append(ev[1].elapsed_time(ev[2]))
+    assert torch.equal(counts, want_counts) and torch.equal(sums, want_sums)
+    total = {k: [r["join_ms"] + t for r, t in zip(runs, torch_ms[k])] for k in ("count", "sum")}
+    total["sum"] = [x + c for x, c in zip(total["sum"], torch_ms["count"])]  # the mask and rids are shared
+    lines["a"] = report("a", "LEFT_OUTER materialize + torch bincount / index_add_", j, runs, {
+        "rows": int(pairs.shape[0]), "torch_count_ms": _spread(torch_ms["count"]), "torch_sum_ms": _spread(torch_ms["sum"]),
+        "total_count_ms": _spread(total["count"]), "total_sum_ms": _spread(total["sum"])})
+    del j, pairs, m, rid, srid, counts, sums
+    ctx.trim_workspace()
+    torch.cuda.empty_cache()
+
+    # ---- b: count-only LEFT_OUTER
+    j = join("LEFT_OUTER", False)
+    for _ in range(a.warmup):
+        j.run()
+    runs = [j.run() for _ in range(a.steps)]
+    assert runs[-1]["matched_pairs"] == pairs_total and runs[-1]["unmatched_inner"] == empty
+    lines["b"] = report("b", "LEFT_OUTER count-only (bpOuterCount)", j, runs)
+    del j
+    ctx.trim_workspace()
+
+    # ---- c: GROUP rows (rid, count)
+    j = join("GROUP", True)
+    for _ in range(a.warmup):
+        j.run()
+    runs = [j.run() for _ in range(a.steps)]
+    rows = j.output_groups().cuda()
+    assert rows.shape == (G_R, 2) and torch.equal(by_rid(rows, 1), want_counts)
+    assert runs[-1]["matched_pairs"] == pairs_total and runs[-1]["unmatched_inner"] == empty
+    lines["c"] = report("c", "GROUP materialize, counts", j, runs, {"rows": G_R})
+    del rows
+
+    # ---- d: GROUP rows (rid, count, sum)
+    runs = []
+    for it in range(a.warmup + a.steps):
+        res, rows = j.join_group(ctx, values, 0, G_S)
+        if it >= a.warmup:
+            runs.append(res)
+    rows = rows.cuda()
+    assert rows.shape == (G_R, 3) and torch.equal(by_rid(rows, 1), want_counts) and torch.equal(by_rid(rows, 2), want_sums)
+    lines["d"] = report("d", "GROUP materialize, counts and sums (join_group)", j, runs, {"rows": G_R})
+
+    a_count, a_sum = lines["a"]["total_count_ms"], lines["a"]["total_sum_ms"]
+    c_med, d_med, b_med = (lines[k]["join_ms"]["median"] for k in ("c", "d", "b"))
+    print(json.dumps({
+        "workload": wl.name, "comparison": "join_ms medians (a: join_ms + torch part)",
+        "a_count": a_count, "a_sum": a_sum, "b": b_med, "c": c_med, "d": d_med,
+        "c_below_a_beyond_spread": a_count["median"] - c_med > a_count["max"] - a_count["min"],
+        "d_below_a_beyond_spread": a_sum["median"] - d_med > a_sum["max"] - a_sum["min"],
+        "c_over_b": round(c_med / b_med, 3),
+        "c_over_b_build_probe": round(lines["c"]["dev_build_probe_ms"]["median"] / lines["b"]["dev_build_probe_ms"]["median"], 3),
+        "checked": "counts and sums equal the oracle"}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
