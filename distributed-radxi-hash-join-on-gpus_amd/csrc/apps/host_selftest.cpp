@@ -8,6 +8,8 @@
 //
 //   host_selftest [--ranks N] [--size G]
 // Exit code 0 iff every join matches its oracle.
+#include <algorithm>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -43,13 +45,15 @@ struct Case {
   bool semiBitmap = false;
   // kind Group: sum an outer value column per group (HashJoin::joinGroup; one rank), else counts only
   bool groupValues = false;
+  // kind Group: sum, min and max of three strided outer columns per group (HashJoin::joinGroupAgg; one rank)
+  bool groupAgg = false;
 };
 
 // The value of outer tuple `rid` in the group-join cases: spread over the int64 range, so the sums wrap.
 uint64_t groupValue(uint64_t rid) { return kernels::mix64(rid + 77) * 0x9E3779B97F4A7C15ull; }
 
 bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
-  if (c.semiBitmap || c.groupValues) ranks = 1;
+  if (c.semiBitmap || c.groupValues || c.groupAgg) ranks = 1;
   auto group = std::make_shared<comm::InProcessGroup>(ranks);
   std::vector<std::string> errors(ranks);
   std::vector<uint64_t> matches(ranks, 0), pairs(ranks, 0);
@@ -87,6 +91,7 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
       cfg.chunks = 2;
       cfg.wireCodec = c.wire ? core::WireCodecMode::On : core::WireCodecMode::Off;
       cfg.semiBitmap = c.semiBitmap;
+      if (c.groupAgg) cfg.groupColumns = 3;
       operators::HashJoin j(&R, &S, &ctx, cfg);
       if (c.semiBitmap && !(j.getPlan().bitmapJoin && j.getPlan().bitmapSet))
         throw std::runtime_error("the set bitmap plan was not taken");
@@ -95,11 +100,26 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
         values.assign(3 * GS, 0);
         for (uint64_t i = 0; i < GS; ++i) values[3 * i + 1] = groupValue(i);
       }
-      operators::JoinResult res = c.groupValues ? j.joinGroup(values.data() + 1, 0, GS, 3) : j.run();
+      kernels::GroupColumns cols;
+      if (c.groupAgg) {  // words 0, 1, 2 of 3-word rows: sum of the first, min of the second, max of the third
+        values.assign(3 * GS, 0);
+        for (uint64_t i = 0; i < 3 * GS; ++i) values[i] = groupValue(i);
+        cols.n = 3;
+        for (uint32_t k = 0; k < 3; ++k) {
+          cols.col[k] = reinterpret_cast<const unsigned long long *>(values.data()) + k;
+          cols.stride[k] = 3;
+        }
+        cols.agg[0] = kernels::GROUP_SUM;
+        cols.agg[1] = kernels::GROUP_MIN;
+        cols.agg[2] = kernels::GROUP_MAX;
+      }
+      operators::JoinResult res = c.groupAgg      ? j.joinGroupAgg(cols, 0, GS)
+                                  : c.groupValues ? j.joinGroup(values.data() + 1, 0, GS, 3)
+                                                  : j.run();
       if (groupKind) {
-        const uint64_t W = c.groupValues ? 3 : 2;
+        const uint64_t W = c.groupAgg ? 5 : c.groupValues ? 3 : 2;
         if (res.localMatches != res.outputGroups || res.unmatchedOuter != 0 || res.outputPairs != 0 ||
-            res.outputRids != 0 || res.groupSums != c.groupValues || !j.getOutputGroups())
+            res.outputRids != 0 || res.groupSums != c.groupValues || res.groupColumns != W - 2 || !j.getOutputGroups())
           throw std::runtime_error("group join: the result fields do not add up");
         groups[r].assign(j.getOutputGroups(), j.getOutputGroups() + res.outputGroups * W);
         uint64_t pairsSum = 0, zeros = 0;
@@ -210,14 +230,26 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
     R.generate(is, 0);
     S.generate(os, 0);
     std::unordered_map<uint64_t, std::pair<uint64_t, uint64_t>> byKey;  // outer key -> (count, sum)
+    struct Agg {
+      uint64_t sum = 0;
+      int64_t min = INT64_MAX, max = INT64_MIN;
+    };
+    std::unordered_map<uint64_t, Agg> aggByKey;  // groupAgg: outer key -> (sum of word 0, min of word 1, max of word 2)
     for (uint64_t i = 0; i < GS; ++i) {
       auto &e = byKey[S.getData()[i].key];
       ++e.first;
       e.second += groupValue(S.getData()[i].rid);
+      if (c.groupAgg) {
+        Agg &g = aggByKey[S.getData()[i].key];
+        const uint64_t rid = S.getData()[i].rid;
+        g.sum += groupValue(3 * rid);
+        g.min = std::min(g.min, (int64_t)groupValue(3 * rid + 1));
+        g.max = std::max(g.max, (int64_t)groupValue(3 * rid + 2));
+      }
     }
     std::unordered_map<uint64_t, uint64_t> keyOf;  // inner rid -> key
     for (uint64_t i = 0; i < G; ++i) keyOf[R.getData()[i].rid] = R.getData()[i].key;
-    const uint64_t W = c.groupValues ? 3 : 2;
+    const uint64_t W = c.groupAgg ? 5 : c.groupValues ? 3 : 2;
     std::unordered_set<uint64_t> seen;
     uint64_t repeated = 0, empty = 0;
     for (const auto &v : groups)
@@ -230,6 +262,10 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
         auto e = byKey.find(k->second);
         const uint64_t cnt = e == byKey.end() ? 0 : e->second.first, sum = e == byKey.end() ? 0 : e->second.second;
         if (v[i + 1] != cnt || (c.groupValues && v[i + 2] != sum)) ok = false;
+        if (c.groupAgg) {  // an empty group carries the identities
+          const Agg g = e == byKey.end() ? Agg() : aggByKey[k->second];
+          if (v[i + 2] != g.sum || (int64_t)v[i + 3] != g.min || (int64_t)v[i + 4] != g.max) ok = false;
+        }
         empty += cnt == 0;
       }
     if (seen.size() != G) ok = false;
@@ -324,6 +360,8 @@ int main(int argc, char **argv) {
        core::JoinKind::Group, false, true},
       {"group_wide_sum", kernels::KeyDistribution::Zipf, true, true, false, core::KeyHashing::Auto, false,
        core::JoinKind::Group, false, true},
+      {"group_zipf_sum_min_max", kernels::KeyDistribution::Zipf, false, true, false, core::KeyHashing::Auto, false,
+       core::JoinKind::Group, false, false, true},
       {"semi_bitmap_zipf_rids", kernels::KeyDistribution::Zipf, false, true, false, core::KeyHashing::Auto, false,
        core::JoinKind::Semi, true},
       {"semi_bitmap_uniform_count", kernels::KeyDistribution::Uniform, false, false, false, core::KeyHashing::Auto,

@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cctype>
 #include <memory>
 #include <tuple>
 #include <vector>
@@ -789,6 +790,138 @@ py::dict opBuildProbeGroup(const at::Tensor &R, const at::Tensor &S, const at::T
   return d;
 }
 
+// columns / aggs of join_group_agg and build_probe_group_agg -> kernels::GroupColumns (offset and rows left to the
+// caller): 1-D int64 tensors of `rows` entries where `device` says, "sum" | "min" | "max" in any letter case.
+static kernels::GroupColumns groupColumnsOf(const char *who, const std::vector<at::Tensor> &columns,
+                                            const std::vector<std::string> &aggs, bool onDevice, int64_t rows) {
+  TORCH_CHECK(!columns.empty() && columns.size() <= kernels::GROUP_MAX_COLUMNS, who, ": ", columns.size(),
+              " value columns; a group join aggregates 1 to ", kernels::GROUP_MAX_COLUMNS);
+  TORCH_CHECK(aggs.size() == columns.size(), who, ": ", aggs.size(), " aggregates for ", columns.size(),
+              " columns (one of sum, min, max per column)");
+  kernels::GroupColumns c;
+  c.n = (uint32_t)columns.size();
+  for (uint32_t i = 0; i < c.n; ++i) {
+    const at::Tensor &v = columns[i];
+    std::string name = aggs[i];
+    for (char &ch : name) ch = (char)std::tolower((unsigned char)ch);
+    TORCH_CHECK(name == "sum" || name == "min" || name == "max", who, ": unknown aggregate '", aggs[i],
+                "' of column ", i, " (sum, min or max; AVG is sum / count on the caller's side)");
+    c.agg[i] = name == "sum" ? kernels::GROUP_SUM : name == "min" ? kernels::GROUP_MIN : kernels::GROUP_MAX;
+    TORCH_CHECK(v.dim() == 1 && v.scalar_type() == at::kLong, who, ": column ", i, " must be a 1-D int64 tensor");
+    TORCH_CHECK(v.size(0) == 0 || v.stride(0) >= 1, who, ": column ", i, " needs a positive element stride");
+    TORCH_CHECK(v.is_cuda() == onDevice, who, ": column ", i, " must live where the join runs");
+    TORCH_CHECK(v.size(0) == rows, who, ": column ", i, " has ", v.size(0), " entries and does not cover the ", rows,
+                " outer rows");
+    c.col[i] = reinterpret_cast<const unsigned long long *>(v.data_ptr());
+    c.stride[i] = v.size(0) ? (uint64_t)v.stride(0) : 1;
+  }
+  return c;
+}
+
+// ---- group join with aggregated value columns over partition-major inputs ----
+// rows: int64 [|R|, 2 + C] (inner rid, count, agg_0, ...); counts [|R|] and aggs [C, |R|]: the raw accumulators by
+// position of R (kernels::groupAggFill / bpGroupAgg / groupEmitAgg and the host twins).
+py::dict opBuildProbeGroupAgg(const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR, const at::Tensor &partS,
+                              int64_t fragShift, int64_t keyShift, bool wide, int64_t rChunk, int64_t sChunk,
+                              const std::vector<at::Tensor> &columns, const std::vector<std::string> &aggs,
+                              int64_t ridOffset) {
+  TORCH_CHECK(R.device() == S.device(), "R and S must live on the same device");
+  TORCH_CHECK(rChunk >= 1 && sChunk >= 1, "r_chunk and s_chunk must be positive");
+  TORCH_CHECK((uint64_t)S.size(0) < (1ull << 32), "build_probe_group_agg: the per-group counters are 32 bits wide");
+  setDevice(R);
+  TORCH_CHECK(!columns.empty(), "build_probe_group_agg: needs at least one value column");
+  kernels::GroupColumns cols = groupColumnsOf("build_probe_group_agg", columns, aggs, R.is_cuda(), columns[0].size(0));
+  for (const at::Tensor &v : columns)
+    TORCH_CHECK(v.device() == R.device(), "build_probe_group_agg: the columns must be on the device of R and S");
+  cols.offset = (uint64_t)ridOffset;
+  cols.rows = (uint64_t)columns[0].size(0);
+  if (S.size(0)) {  // every outer rid must have a value
+    at::Tensor rid = wide ? S.select(1, 1) : at::bitwise_and(S.reshape({-1}), keyShift >= 64 ? -1 : ((int64_t(1) << keyShift) - 1));
+    const int64_t lo = rid.min().item<int64_t>(), hi = rid.max().item<int64_t>();
+    TORCH_CHECK(lo >= ridOffset && hi - ridOffset < (int64_t)cols.rows, "build_probe_group_agg: values [", ridOffset, ", ",
+                ridOffset + (int64_t)cols.rows, ") do not cover the outer rids [", lo, ", ", hi, "]");
+  }
+  kernels::BPArgs a;
+  a.R = R.data_ptr();
+  a.S = S.data_ptr();
+  at::Tensor pr = partR.to(R.device()).contiguous(), ps = partS.to(R.device()).contiguous();
+  TORCH_CHECK(pr.size(0) == ps.size(0) && pr.size(0) >= 1, "part_r and part_s must have the same P + 1 entries");
+  a.partR = ptr<uint64_t>(pr);
+  a.partS = ptr<uint64_t>(ps);
+  a.P = (uint32_t)pr.size(0) - 1;
+  a.rChunk = (uint32_t)rChunk;
+  a.sChunk = (uint32_t)sChunk;
+  a.fragShift = (uint32_t)fragShift;
+  a.keyShift = (uint32_t)keyShift;
+  a.wide = wide;
+  const int64_t nR = R.size(0), nS = S.size(0), C = cols.n, W = 2 + C, slots = nR + 2;
+  at::Tensor accCount = at::zeros({slots}, like(R, at::kInt)), accAgg = at::empty({C, slots}, like(R));
+  at::Tensor rows = at::empty({nR, W}, like(R));
+  uint64_t matched = 0, zeros = 0;
+  if (R.is_cuda()) {
+    at::Tensor ctr = at::zeros({8}, like(R));
+    auto *c = reinterpret_cast<unsigned long long *>(ctr.data_ptr());
+    a.result = c;
+    uint32_t *nItems = reinterpret_cast<uint32_t *>(c + 2), *nUnits = reinterpret_cast<uint32_t *>(c + 6);
+    const int64_t P1 = std::max<int64_t>(a.P, 1);
+    at::Tensor counts = at::empty({P1}, like(R, at::kInt)), offsets = at::empty({P1}, like(R, at::kInt));
+    kernels::BPArgs ua = kernels::outerSwapSides(a, std::min<uint32_t>(a.rChunk, kernels::MARK_UNIT));
+    ua.result = c + 4;
+    const uint32_t unitCap = a.P + (uint32_t)(nR / ua.sChunk) + 1;
+    uint32_t capacity = 2 * a.P + (uint32_t)(nS / a.sChunk + nR / a.rChunk) + 1024;
+    at::Tensor items, scanWs;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      items = at::empty({(int64_t)capacity * 2}, like(R));
+      scanWs = at::empty({(int64_t)kernels::scanWorkspaceBytes(std::max<uint64_t>(a.P, unitCap)) / 4 + 1},
+                         like(R, at::kInt));
+      ctr.zero_();
+      accCount.zero_();
+      kernels::groupAggFill(cols, ptr<unsigned long long>(accAgg), (uint64_t)slots, nullptr);
+      kernels::bpPlanCounts(a, ptr<uint32_t>(counts), nullptr);
+      kernels::scanExclusiveU32(ptr<uint32_t>(counts), ptr<uint32_t>(offsets), a.P, nItems, scanWs.data_ptr(), nullptr);
+      kernels::bpEmit(a, ptr<uint32_t>(counts), ptr<uint32_t>(offsets), ptr<kernels::BPItem>(items), capacity, nullptr);
+      kernels::bpGroupAgg(a, ptr<kernels::BPItem>(items), nItems, capacity, cols, ptr<uint32_t>(accCount),
+                          ptr<unsigned long long>(accAgg), (uint64_t)slots, nullptr);
+      HIP_CHECK(hipDeviceSynchronize());
+      const uint32_t need = (uint32_t)(ctr.cpu()[2].item<int64_t>() & 0xFFFFFFFF);
+      if (need <= capacity) break;
+      TORCH_CHECK(attempt == 0, "build_probe_group_agg: the work-item list overflowed twice");
+      capacity = need;
+    }
+    at::Tensor units = at::empty({(int64_t)unitCap}, like(R)), unitCounts = at::zeros({(int64_t)unitCap}, like(R, at::kInt)),
+               unitOffsets = at::empty({(int64_t)unitCap}, like(R));
+    kernels::markPlanUnits(ua, ptr<uint32_t>(counts), nullptr);
+    kernels::scanExclusiveU32(ptr<uint32_t>(counts), ptr<uint32_t>(offsets), a.P, nUnits, scanWs.data_ptr(), nullptr);
+    kernels::markEmitUnits(ua, ptr<uint32_t>(counts), ptr<uint32_t>(offsets), ptr<kernels::MarkUnit>(units), unitCap,
+                           nullptr);
+    kernels::groupUnitLengths(ua, ptr<kernels::MarkUnit>(units), nUnits, unitCap, ptr<uint32_t>(unitCounts), nullptr);
+    kernels::scanExclusiveU32to64(ptr<uint32_t>(unitCounts), ptr<unsigned long long>(unitOffsets), unitCap, c + 1,
+                                  scanWs.data_ptr(), nullptr);
+    kernels::groupEmitAgg(ua, ptr<kernels::MarkUnit>(units), nUnits, unitCap, ptr<uint32_t>(accCount),
+                          ptr<unsigned long long>(accAgg), (uint64_t)slots, cols.n, ptr<unsigned long long>(unitOffsets),
+                          ptr<unsigned long long>(rows), (uint64_t)nR, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    at::Tensor h = ctr.cpu();
+    matched = (uint64_t)h[0].item<int64_t>();
+    zeros = (uint64_t)h[4].item<int64_t>();
+    TORCH_CHECK(h[1].item<int64_t>() == nR, "build_probe_group_agg: the partitions hold ", h[1].item<int64_t>(),
+                " inner tuples, R has ", nR);
+  } else {
+    uint64_t n = 0;
+    matched = host::buildProbeGroupAgg(a, cols, ptr<uint32_t>(accCount), ptr<uint64_t>(accAgg), (uint64_t)slots);
+    zeros = host::groupEmitAgg(a, ptr<uint32_t>(accCount), ptr<uint64_t>(accAgg), (uint64_t)slots, cols.n,
+                               ptr<uint64_t>(rows), (uint64_t)nR, &n);
+    TORCH_CHECK((int64_t)n == nR, "build_probe_group_agg: the partitions hold ", n, " inner tuples, R has ", nR);
+  }
+  py::dict d;
+  d["rows"] = rows;
+  d["counts"] = accCount.narrow(0, 0, nR).to(at::kLong);
+  d["aggs"] = accAgg.narrow(1, 0, nR).contiguous();
+  d["matched_pairs"] = matched;
+  d["unmatched_inner"] = zeros;
+  return d;
+}
+
 at::Tensor opGenerate(int64_t n, int64_t globalOffset, int64_t globalSize, const data::GenSpec &spec,
                       const std::string &device) {
   at::Tensor out = at::empty({n, 2}, at::TensorOptions().dtype(at::kLong).device(device));
@@ -1345,6 +1478,7 @@ py::dict resultToDict(const operators::JoinResult &r) {
   d["output_pairs"] = r.outputPairs;
   d["output_rids"] = r.outputRids;
   d["output_groups"] = r.outputGroups;
+  d["group_columns"] = r.groupColumns;
   d["matched_pairs"] = r.matchedPairs;
   d["unmatched_inner"] = r.unmatchedInner;
   d["unmatched_outer"] = r.unmatchedOuter;
@@ -1411,10 +1545,11 @@ static py::dict statsToDict(const operators::LateMaterialization::Stats &st) {
 }
 
 // kind = GROUP with materialize: the rows of the last run(), int64 [m, 2]
-// (inner rid, count) or [m, 3] (inner rid, count, sum), any order.
+// (inner rid, count), [m, 3] (inner rid, count, sum) or [m, 2 + C] (inner rid,
+// count, agg_0, ..., agg_{C-1}), any order.
 static at::Tensor groupRows(operators::HashJoin &j) {
   const auto &r = j.lastResult();
-  const int64_t n = (int64_t)r.outputGroups, W = r.groupSums ? 3 : 2;
+  const int64_t n = (int64_t)r.outputGroups, W = 2 + (int64_t)r.groupColumns;
   at::Tensor out = at::empty({n, W}, at::kLong);
   if (n && j.getOutputGroups()) {
     HJ_CHECK(j.outputGroupsValid(),
@@ -1590,6 +1725,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "materializing join writes its pairs there instead of the workspace (0 = workspace)")
       .def_readwrite("build_target", &core::JoinConfig::buildTarget)
       .def_readwrite("r_chunk", &core::JoinConfig::rChunk)
+      .def_readwrite("group_columns", &core::JoinConfig::groupColumns)
       .def_readwrite("s_chunk", &core::JoinConfig::sChunk)
       .def_readwrite("chunks", &core::JoinConfig::chunks)
       .def_readwrite("checks", &core::JoinConfig::checks)
@@ -1645,6 +1781,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         return std::vector<uint32_t>{p.wireBits[0], p.wireBits[1]};
       })
       .def_readonly("r_chunk", &core::JoinPlan::rChunk)
+      .def_readonly("group_columns", &core::JoinPlan::groupColumns)
       .def_readonly("s_chunk", &core::JoinPlan::sChunk)
       .def_readonly("chunks", &core::JoinPlan::chunks)
       .def_readonly("two_level", &core::JoinPlan::twoLevel)
@@ -2195,6 +2332,32 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
             return py::make_tuple(resultToDict(r), groupRows(j));
           },
           py::arg("context"), py::arg("outer_values"), py::arg("outer_rid_offset") = 0, py::arg("outer_global_rows") = 0)
+      .def(
+          "join_group_agg",
+          [](operators::HashJoin &j, std::shared_ptr<core::ExecContext> ctx, std::vector<at::Tensor> columns,
+             std::vector<std::string> aggs, uint64_t outerOffset, uint64_t outerGlobal) {
+            // One kind=GROUP join that aggregates 1 ... 4 outer value columns per group, each by "sum", "min" or
+            // "max": (result dict, rows [|R|, 2 + C] of (rid, count, agg_0, ...)).  Columns: 1-D int64, any
+            // positive element stride each (views of one payload tensor, or separate tensors).
+            TORCH_CHECK(j.getConfig().kind == core::JoinKind::Group, "join_group_agg needs kind=GROUP, this join has kind=",
+                        core::joinKindName(j.getConfig().kind));
+            TORCH_CHECK(j.spillPasses() == 1, "join_group_agg: value columns cannot be combined with a capacity spill (",
+                        j.spillPasses(), " passes)");
+            TORCH_CHECK(j.getConfig().materialize, "join_group_agg needs materialize=True");
+            TORCH_CHECK(columns.size() <= kernels::GROUP_MAX_COLUMNS, "join_group_agg: ", columns.size(),
+                        " value columns; a group join aggregates 1 to ", kernels::GROUP_MAX_COLUMNS);
+            kernels::GroupColumns cols =
+                groupColumnsOf("join_group_agg", columns, aggs, j.context()->onDevice(), (int64_t)outerGlobal);
+            if (j.context()->onDevice()) HIP_CHECK(hipDeviceSynchronize());  // values written on other streams
+            operators::JoinResult r;
+            {
+              py::gil_scoped_release nogil;
+              r = j.joinGroupAgg(cols, outerOffset, outerGlobal);
+            }
+            return py::make_tuple(resultToDict(r), groupRows(j));
+          },
+          py::arg("context"), py::arg("columns"), py::arg("aggs"), py::arg("outer_rid_offset") = 0,
+          py::arg("outer_global_rows") = 0)
       .def("output_rids", [](operators::HashJoin &j) {
         // kind = SEMI / ANTI with materialize: the qualifying outer rids, int64 [m], any order.
         const uint64_t n = j.lastResult().outputRids;
@@ -2376,6 +2539,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   ops.def("build_probe_outer", &opBuildProbeOuter, py::arg("R"), py::arg("S"), py::arg("part_r"), py::arg("part_s"),
           py::arg("frag_shift"), py::arg("key_shift"), py::arg("wide") = false, py::arg("r_chunk") = 4096,
           py::arg("s_chunk") = 65536, py::arg("keep_inner") = true, py::arg("keep_outer") = true);
+  ops.def("build_probe_group_agg", &opBuildProbeGroupAgg, py::arg("R"), py::arg("S"), py::arg("part_r"), py::arg("part_s"),
+          py::arg("frag_shift"), py::arg("key_shift"), py::arg("wide"), py::arg("r_chunk"), py::arg("s_chunk"),
+          py::arg("columns"), py::arg("aggs"), py::arg("rid_offset") = 0);
   ops.def("build_probe_group", &opBuildProbeGroup, py::arg("R"), py::arg("S"), py::arg("part_r"), py::arg("part_s"),
           py::arg("frag_shift"), py::arg("key_shift"), py::arg("wide") = false, py::arg("r_chunk") = 4096,
           py::arg("s_chunk") = 65536, py::arg("values") = py::none(), py::arg("rid_offset") = 0);

@@ -10,18 +10,19 @@ namespace core {
 
 std::string JoinConfig::describe() const {
   return utils::format("JoinConfig(networkBits=%u localBits=%u twoLevel=%d keyShift=%u assignment=%s format=%s "
-                       "materialize=%d buildTarget=%lu rChunk=%u sChunk=%u chunks=%u%s%s)",
+                       "materialize=%d buildTarget=%lu rChunk=%u sChunk=%u chunks=%u%s%s%s)",
                        networkBits, localBits, (int)twoLevel, keyShift,
                        assignment == AssignmentPolicy::LPT ? "lpt" : "round_robin",
                        format == TupleFormat::Wide ? "wide" : "compressed", (int)materialize,
                        (unsigned long)buildTarget, rChunk, sChunk, chunks, kind == JoinKind::Inner ? "" : " kind=",
-                       kind == JoinKind::Inner ? "" : joinKindName(kind));
+                       kind == JoinKind::Inner ? "" : joinKindName(kind),
+                       kind == JoinKind::Group ? utils::format(" groupColumns=%u", groupColumns).c_str() : "");
 }
 
 std::string JoinPlan::describe() const {
   return utils::format("JoinPlan(nodes=%u networkBits=%u localBits=%u twoLevel=%d keyShift=%u fragShift=%u "
                        "rChunk=%u sChunk=%u chunks=%u wide=%d materialize=%d keyMix=%d sampled=%d assignment=%s wire=%u/%u "
-                       "split=%d splitHist=%d pipeOuter=%d bitmap=%d/%u%s%s%s%s%s%s%s%s)",
+                       "split=%d splitHist=%d pipeOuter=%d bitmap=%d/%u%s%s%s%s%s%s%s%s%s)",
                        numberOfNodes, networkBits, localBits, (int)twoLevel, keyShift, fragShift, rChunk, sChunk,
                        chunks, (int)wide, (int)materialize, (int)keyMix, (int)sampledNetwork,
                        assignment == AssignmentPolicy::LPT ? "lpt" : "round_robin", wireBits[0], wireBits[1],
@@ -29,7 +30,8 @@ std::string JoinPlan::describe() const {
                        bitmapSet ? " bitmapSet" : "", bitmapReplicated ? " replicated" : "", keyOnly ? " keyOnly" : "",
                        oneSided ? " oneSided" : "", fragments && !bitmapJoin ? " fragments" : "",
                        innerRepeats ? " innerRepeats" : "", kind == JoinKind::Inner ? "" : " kind=",
-                       kind == JoinKind::Inner ? "" : joinKindName(kind));
+                       kind == JoinKind::Inner ? "" : joinKindName(kind),
+                       kind == JoinKind::Group ? utils::format(" groupColumns=%u", groupColumns).c_str() : "");
 }
 
 JoinPlan makePlan(const JoinConfig &cfg, uint32_t numberOfNodes, uint64_t globalInner, uint64_t globalOuter,
@@ -40,6 +42,10 @@ JoinPlan makePlan(const JoinConfig &cfg, uint32_t numberOfNodes, uint64_t global
   p.wide = cfg.format == TupleFormat::Wide;
   p.materialize = cfg.materialize;
   p.kind = cfg.kind;
+  JOIN_ASSERT(cfg.groupColumns >= 1 && cfg.groupColumns <= kernels::GROUP_MAX_COLUMNS, "Plan",
+              "JoinConfig.groupColumns (group_columns) = %u: a group join aggregates 1 to %u value columns",
+              cfg.groupColumns, kernels::GROUP_MAX_COLUMNS);
+  p.groupColumns = cfg.groupColumns;
   p.directCount = cfg.directCount;
   p.localItemTiles = std::max<uint32_t>(1, std::min<uint32_t>(cfg.localItemTiles, 1024));
   p.variants = cfg.variants;
@@ -113,7 +119,15 @@ JoinPlan makePlan(const JoinConfig &cfg, uint32_t numberOfNodes, uint64_t global
   }
   // Group joins: final partitions of one LDS table (rChunk below), so that no
   // outer tuple is probed against several inner chunks.
-  if (group && !cfg.rChunk) splitBits(std::min<uint64_t>(cfg.buildTarget, p.wide ? 1024 : 2048));
+  // Keys, u32 counters and groupColumns u64 accumulators per slot
+  // (kernels::bpGroup, bpGroupAgg).  Whether value columns come is known only
+  // at run time, so the table is sized with them: the largest rChunk whose
+  // table lets two workgroups share a CU (80 KiB each).  One column: 2048 (64
+  // KiB + 64 B; wide 80 KiB + 64 B -> 1024, 40 KiB); two or three: 1024; four: 512.
+  uint32_t groupChunk = 4096;
+  while (group && groupChunk > 64 && kernels::groupTableBytes(groupChunk, p.wide, p.groupColumns) > 80 * 1024)
+    groupChunk /= 2;
+  if (group && !cfg.rChunk) splitBits(std::min<uint64_t>(cfg.buildTarget, groupChunk));
   if (p.keyOnly) {
     // 8-byte table entries: final partitions of <= 2048 inner tuples give 36 KiB
     // LDS tables (4 workgroups per CU).  Measured on 1B x 1B sparse keys:
@@ -155,12 +169,7 @@ JoinPlan makePlan(const JoinConfig &cfg, uint32_t numberOfNodes, uint64_t global
   if (cfg.rChunk) {
     p.rChunk = cfg.rChunk;
   } else if (group) {
-    // Keys, u32 counters and u64 sums per slot (kernels::bpGroup).  Whether a
-    // value column comes is known only at run time, so the table is sized with
-    // it: the largest rChunk whose table lets two workgroups share a CU (80
-    // KiB each): 2048 (64 KiB + 64 B; wide 80 KiB + 64 B -> 1024, 40 KiB).
-    p.rChunk = 4096;
-    while (p.rChunk > 64 && kernels::groupTableBytes(p.rChunk, p.wide, true) > 80 * 1024) p.rChunk /= 2;
+    p.rChunk = groupChunk;
   } else {
     const uint32_t entry = p.wide ? (pairs ? 16 : 8) : (pairs || p.keyOnly ? 8 : 4);
     const uint32_t budget = (entry == 4 || p.keyOnly) ? 32 * 1024 : matNarrow ? 16 * matTarget : 64 * 1024;

@@ -84,8 +84,13 @@ enum class ExchangeMode : int {
 //     row per inner tuple, also those without a partner: (inner rid, count)
 //     where count is the number of outer tuples with its key, or (inner rid,
 //     count, sum) with an outer value column (HashJoin::joinGroup; int64, the
-//     sum wraps).  Copies of an inner key each get the key's full count and
-//     sum.  No pair is formed (kernels/group_join.hip).  local_matches /
+//     sum wraps), or (inner rid, count, agg_0, ..., agg_{C-1}) over C = 1 ...
+//     4 outer value columns, each with its own SUM, signed MIN or signed MAX
+//     (HashJoin::joinGroupAgg; JoinConfig::groupColumns sizes the LDS tables;
+//     an empty group carries each aggregate's identity: 0, INT64_MAX,
+//     INT64_MIN; AVG is sum / count on the caller's side).  Copies of an inner
+//     key each get the key's full count and aggregates.  No pair is formed
+//     (kernels/group_join.hip).  local_matches /
 //     global_matches count the result rows (this rank's inner tuples);
 //     matchedPairs is the sum of the counts (the inner join's count),
 //     unmatchedInner the groups with count 0, unmatchedOuter 0.
@@ -136,8 +141,11 @@ struct JoinConfig {
   uint64_t buildTarget = 4096;  // target inner tuples per final partition (= one 256 x 16 LDS build batch)
   uint32_t rChunk = 0;          // max inner tuples per LDS table (0 = auto from LDS budget)
   uint32_t sChunk = 65536;      // max outer tuples per build/probe work item
+  // kind Group: the most value columns a run may aggregate (1 ... 4; HashJoin::joinGroupAgg).  The automatic
+  // rChunk leaves room for this many 8-byte accumulators per LDS slot; a run with more columns is refused.
+  uint32_t groupColumns = 1;
   uint32_t chunks = 1;          // exchange pipeline slices per relation (>1: scatter(k+1) || all-to-all(k))
-  bool checks = true;           // cheap always-on invariants (all tuples written, sizes)
+  bool checks = true;          // cheap always-on invariants (all tuples written, sizes)
   // Network-pass grid cap: 512 = two workgroups per CU, each walking a long
   // contiguous range (1B tuples: 477 tiles per workgroup).  Same-process A/B
   // on MI355X, 1B x 1B: general path 19.23 -> 18.99 ms, headline 9.54 -> 9.47
@@ -225,6 +233,7 @@ struct JoinPlan {
   uint32_t keyBits = 64;      // bits of the largest key over both relations
   uint32_t rChunk = 4096;
   uint32_t sChunk = 65536;
+  uint32_t groupColumns = 1;  // kind Group: value columns the LDS table was sized for (JoinConfig::groupColumns)
   uint32_t chunks = 1;
   bool twoLevel = true;
   bool wide = false;

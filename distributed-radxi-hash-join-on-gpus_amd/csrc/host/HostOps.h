@@ -102,6 +102,14 @@ uint64_t buildProbeGroup(const kernels::BPArgs &a, const uint64_t *values, uint6
                          uint32_t *accCount, uint64_t *accSum);
 uint64_t groupEmit(const kernels::BPArgs &a, const uint32_t *accCount, const uint64_t *accSum, uint64_t *out,
                    uint64_t outCapacity, uint64_t *rows);
+// The same with cols.n aggregated value columns (twins of kernels::bpGroupAgg /
+// groupEmitAgg): accAgg is column-major, accAgg[c * accSlots + r], and is set
+// here to every column's identity first (accCount is zeroed by the caller).
+// Rows are (rid, count, agg_0, ..., agg_{columns-1}).
+uint64_t buildProbeGroupAgg(const kernels::BPArgs &a, const kernels::GroupColumns &cols, uint32_t *accCount,
+                            uint64_t *accAgg, uint64_t accSlots);
+uint64_t groupEmitAgg(const kernels::BPArgs &a, const uint32_t *accCount, const uint64_t *accAgg, uint64_t accSlots,
+                      uint32_t columns, uint64_t *out, uint64_t outCapacity, uint64_t *rows);
 
 // Wire codec (kernels.h, WireCodec) over host segment lists.
 void wirePack(const uint64_t *raw, uint64_t *wire, const kernels::WireSeg *segs, uint32_t nSegs,

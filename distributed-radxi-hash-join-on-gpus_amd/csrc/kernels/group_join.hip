@@ -1,7 +1,11 @@
 // Group joins (core::JoinKind::Group): per inner tuple r the number of outer
 // tuples with r's key, and optionally the int64 sum (two's complement, wraps)
 // of one outer value column over those tuples -- the join followed by COUNT /
-// SUM ... GROUP BY the build side, without ever forming a pair.
+// SUM ... GROUP BY the build side, without ever forming a pair.  With
+// aggregated value columns (GroupColumns): C = 1 ... 4 outer columns, each with
+// its own base pointer, stride and aggregate -- SUM (wraps), signed MIN or
+// signed MAX -- and rows (rid, count, agg_0, ..., agg_{C-1}).  AVG is sum /
+// count on the caller's side and is not built.
 //
 //  * bpGroupKernel<LAYOUT, DIRECT, SUM> -- persistent grid over the BPItem
 //    list, geometry of bpOuterCountKernel (256 threads, 16 tuples per thread
@@ -44,6 +48,30 @@
 //    shuffles).  Zero counts are added to *a.result; without `out` the kernel
 //    only counts them.  Positions outside [partS, partSEnd) -- the gaps of a
 //    sampled local pass -- are never read.
+//  * bpGroupAggKernel<LAYOUT, C> -- bpGroupKernel<LAYOUT, hashed, SUM> with C
+//    8-byte accumulators per slot (column-major in LDS) and the columns passed
+//    by value (C pointers, strides and aggregate codes; the code is
+//    wave-uniform and branched on at run time: the kernel is templated on C
+//    only).  The table clear writes each accumulator's identity (0, INT64_MAX,
+//    INT64_MIN), not zeros.  The probe does the u32 add and one 64-bit LDS
+//    atomic per column: add, signed min or signed max.  The gathers of G
+//    tuples (C * G values) are issued before the first is consumed; G shrinks
+//    with C (16, 8, 4, 4; wide tuples 8, 4, 2, 2) so that nothing spills.  The
+//    inner side applies count and aggregates to global accumulators kept
+//    column-major, acc[c * accSlots + position]: 64-bit atomic add, signed min,
+//    signed max.  These must hold the identities before the launch:
+//    groupAggFillKernel writes them before every run (a memset cannot).
+//    The 64-bit atomics are native on gfx950 -- the assembly of this file holds
+//    ds_add_u64 / ds_min_i64 / ds_max_i64 and global_atomic_add_x2 / smin_x2 /
+//    smax_x2 and no compare-and-swap loop for them (read once, hipcc of ROCm
+//    7; the only ds_cmpst is the slot claim of the build).
+//    No direct-addressed variant, for the reasons given for SUM above.  One
+//    column with SUM runs bpGroupKernel itself (bpGroupAgg() routes it).
+//  * groupEmitAggKernel<LAYOUT, C> -- groupEmitKernel<LAYOUT, SUM> with W = 2 +
+//    C words per row (4 to 6; one column takes groupEmitKernel's three): word q
+//    of the wave's run is stored by lane q % 64, so the stores stay consecutive
+//    8-byte words although W is no power of two.  Empty groups carry the
+//    identities the fill wrote.
 //
 // Count accumulators are u32: the caller refuses a global outer size of 2^32
 // or more (HashJoin, ops.build_probe_group).
@@ -61,10 +89,18 @@
 //   bpGroupKernel<wide, SUM>         192 VGPRs; 2 workgroups per CU
 //   groupEmitKernel                  28-30 VGPRs (rid, count), 52-54 (rid, count, sum); 32 B LDS
 //   groupUnitLengthsKernel           12 VGPRs, no LDS
+//   bpGroupAggKernel<compressed, C>  238 / 240 / 234 / 248 VGPRs for C = 1 / 2 / 3 / 4; 2 workgroups per CU
+//   bpGroupAggKernel<split, C>       186 / 188 / 182 / 196 VGPRs; 2 workgroups per CU
+//   bpGroupAggKernel<wide, C>        212 / 206 / 200 / 206 VGPRs; 2 workgroups per CU
+//   groupEmitAggKernel<*, C>         62-64 / 73-76 / 86-87 VGPRs for C = 2 / 3 / 4; 32 B LDS
+//   groupAggFillKernel               10 VGPRs, no LDS
 //   LDS of bpGroupKernel (dynamic, bpGroupLdsBytes): hashed 4-byte keys + counters 32 KiB + 64 B at the
 //   planned rChunk 2048 (4096 slots), with sums 64 KiB + 64 B; 8-byte keys at the planned rChunk 1024 (2048
 //   slots) 24 KiB + 64 B, with sums 40 KiB + 64 B; direct 4 B << fragBits + 64 B (32 KiB + 64 B at 13 bits).
 //   A request above 160 KiB (a configured rChunk of 8192 with sums) is refused by bpGroup.
+//   LDS of bpGroupAggKernel: slots * (key + 4 + 8 C) + 64 B -- 4-byte keys at the planned rChunk 2048 / 1024 /
+//   1024 / 512 for C = 1 / 2 / 3 / 4: 64 / 48 / 64 / 40 KiB + 64 B; 8-byte keys at 1024 / 1024 / 1024 / 512: 40 /
+//   56 / 72 / 44 KiB + 64 B (two workgroups per CU each); above 160 KiB refused by bpGroupAgg.
 #include "kernels.h"
 #include "device_common.h"
 #include "mark_units.h"
@@ -308,6 +344,192 @@ __global__ __launch_bounds__(GJ_T, LAYOUT == MK_WIDE || SUM ? 2 : LAYOUT == MK_S
   if (t == 0 && total) atomicAdd(a.result, total);
 }
 
+// ------------------------------------------------------ aggregated columns
+// Values of one column in flight per thread before the first is consumed: 16 (wide tuples 8) divided by the
+// columns, as a power of two -- C * G 8-byte values next to the keys and rids of both sides.
+constexpr int groupAggBatch(int layout, int c) {
+  const int g = (layout == MK_WIDE ? 8 : GJ_K) / c;
+  return g >= 16 ? 16 : g >= 8 ? 8 : g >= 4 ? 4 : 2;
+}
+
+// The aggregate code is wave-uniform (a kernel argument): one scalar branch per atomic.
+__device__ __forceinline__ void groupAggLds(unsigned long long *p, unsigned long long v, uint32_t agg) {
+  if (agg == GROUP_SUM)
+    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  else if (agg == GROUP_MIN)
+    __hip_atomic_fetch_min(reinterpret_cast<long long *>(p), (long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  else
+    __hip_atomic_fetch_max(reinterpret_cast<long long *>(p), (long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void groupAggGlobal(unsigned long long *p, unsigned long long v, uint32_t agg) {
+  if (agg == GROUP_SUM)
+    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else if (agg == GROUP_MIN)
+    __hip_atomic_fetch_min(reinterpret_cast<long long *>(p), (long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else
+    __hip_atomic_fetch_max(reinterpret_cast<long long *>(p), (long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Every column's identity over its accSlots accumulators (column-major).
+__global__ __launch_bounds__(GJ_T) void groupAggFillKernel(GroupColumns cols, unsigned long long *__restrict__ accAgg,
+                                                          uint64_t accSlots) {
+  for (uint32_t c = 0; c < cols.n; ++c) {
+    const unsigned long long ident = groupAggIdentity(cols.agg[c]);
+    for (uint64_t i = (uint64_t)blockIdx.x * GJ_T + threadIdx.x; i < accSlots; i += (uint64_t)gridDim.x * GJ_T)
+      accAgg[c * accSlots + i] = ident;
+  }
+}
+
+// bpGroupKernel<LAYOUT, false, true> with C accumulators per slot, each with its own column and aggregate.
+template <int LAYOUT, int C>
+__global__ __launch_bounds__(GJ_T, 2) void bpGroupAggKernel(BPArgs a, const BPItem *__restrict__ items,
+                                                            const uint32_t *__restrict__ nItemsPtr, uint32_t capacity,
+                                                            GroupColumns cols, uint32_t *accCount,
+                                                            unsigned long long *accAgg, uint64_t accSlots) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  using K = typename GroupKey<LAYOUT>::type;
+  using R = typename GroupRid<LAYOUT>::type;
+  constexpr K EMPTY = LAYOUT == MK_WIDE ? (K)GJ_EMPTY64 : (K)GJ_EMPTY32;
+  constexpr uint32_t BATCH = GJ_T * GJ_K;
+  constexpr bool PRE_RID = LAYOUT != MK_WIDE;  // wide tuples read their rid when a slot was found
+  constexpr int G = groupAggBatch(LAYOUT, C);
+  const uint64_t maxSlots = groupMaxSlots(a.rChunk);
+  // [agg u64 x slots] x C (column-major) [key x slots][count u32 x slots][8 x u64 reduction words]
+  unsigned long long *aggs = reinterpret_cast<unsigned long long *>(smem);
+  K *table = reinterpret_cast<K *>(smem + maxSlots * 8 * C);
+  uint32_t *cnt = reinterpret_cast<uint32_t *>(smem + maxSlots * (8 * C + sizeof(K)));
+  unsigned long long *wsum = reinterpret_cast<unsigned long long *>(smem + maxSlots * (8 * C + sizeof(K) + 4));
+  const uint32_t t = threadIdx.x;
+  const uint32_t nItems = min(*nItemsPtr, capacity);
+  const uint64_t ridMask = a.keyShift >= 64 ? ~0ull : ((1ull << a.keyShift) - 1);
+  unsigned long long ident[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) ident[c] = groupAggIdentity(cols.agg[c]);
+  unsigned long long matches = 0;
+  for (uint32_t w = blockIdx.x; w < nItems; w += gridDim.x) {
+    const BPItem it = items[w];
+    const uint64_t rb = a.partR[it.part] + (uint64_t)it.rChunk * a.rChunk;
+    const uint64_t re = min(a.partREnd[it.part], rb + a.rChunk);
+    const uint64_t sb = a.partS[it.part] + (uint64_t)it.sChunk * a.sChunk;
+    const uint64_t se = min(a.partSEnd[it.part], sb + a.sChunk);
+    const uint32_t nr = (uint32_t)(re - rb), ns = (uint32_t)(se - sb);
+    uint32_t tbits = ceilLog2(2ull * nr);
+    if (tbits < 6) tbits = 6;
+    const uint32_t slots = 1u << tbits, mask = slots - 1;
+
+    // First inner batch and first outer batch are in flight while the table is cleared.
+    K rv[GJ_K], sv[GJ_K];
+    R rr[PRE_RID ? GJ_K : 1], nor[1];
+    if (nr >= BATCH) groupLoad<LAYOUT, true, false>(a.R, a.Rhi, rb, nr, 0, a.fragShift, rv, nor);
+    else groupLoad<LAYOUT, false, false>(a.R, a.Rhi, rb, nr, 0, a.fragShift, rv, nor);
+    if (ns >= BATCH) groupLoad<LAYOUT, true, PRE_RID>(a.S, a.Shi, sb, ns, 0, a.fragShift, sv, rr);
+    else groupLoad<LAYOUT, false, PRE_RID>(a.S, a.Shi, sb, ns, 0, a.fragShift, sv, rr);
+    for (uint32_t i = t; i < slots; i += GJ_T) {
+      cnt[i] = 0;
+      table[i] = EMPTY;
+#pragma unroll
+      for (int c = 0; c < C; ++c) aggs[c * maxSlots + i] = ident[c];  // not all zeros: MIN and MAX
+    }
+    __syncthreads();
+
+    // ---- build: every inner copy takes a slot
+    for (uint32_t b0 = 0; b0 < nr; b0 += BATCH) {
+      if (b0) groupLoad<LAYOUT, false, false>(a.R, a.Rhi, rb, nr, b0, a.fragShift, rv, nor);
+#pragma unroll
+      for (int k = 0; k < GJ_K; ++k) {
+        if (b0 + k * GJ_T + t < nr) {
+          const K key = rv[k];
+          uint32_t h = groupHash<LAYOUT>(key, tbits);
+          while (atomicCAS(&table[h], EMPTY, key) != EMPTY) h = (h + 1) & mask;
+        }
+      }
+    }
+    __syncthreads();
+
+    // ---- probe: the first slot of the key, one u32 LDS atomic and one 64-bit LDS atomic per column
+    for (uint32_t b0 = 0; b0 < ns; b0 += BATCH) {
+      if (b0) {
+        if (b0 + BATCH <= ns) groupLoad<LAYOUT, true, PRE_RID>(a.S, a.Shi, sb, ns, b0, a.fragShift, sv, rr);
+        else groupLoad<LAYOUT, false, PRE_RID>(a.S, a.Shi, sb, ns, b0, a.fragShift, sv, rr);
+      }
+      // G tuples at a time: their slots, then all C * G gathers issued before the first value is consumed.
+#pragma unroll
+      for (int g0 = 0; g0 < GJ_K; g0 += G) {
+        uint32_t slot[G];
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+          slot[j] = GJ_NONE;
+          if (b0 + (g0 + j) * GJ_T + t < ns) {
+            const K key = sv[g0 + j];
+            uint32_t h = groupHash<LAYOUT>(key, tbits);
+            K e;
+            while ((e = table[h]) != EMPTY) {
+              if (e == key) {
+                slot[j] = h;
+                break;
+              }
+              h = (h + 1) & mask;
+            }
+          }
+        }
+        unsigned long long wrid[PRE_RID ? 1 : G];
+        if constexpr (!PRE_RID) {
+#pragma unroll
+          for (int j = 0; j < G; ++j)
+            if (slot[j] != GJ_NONE)
+              wrid[j] = reinterpret_cast<const unsigned long long *>(a.S)[2 * (sb + b0 + (g0 + j) * GJ_T + t) + 1];
+        }
+        unsigned long long val[C][G];
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+          if (slot[j] != GJ_NONE) {  // a tuple that found no slot forms no address
+            uint64_t rid;
+            if constexpr (!PRE_RID) rid = wrid[j];
+            else rid = LAYOUT == MK_COMPRESSED ? ((uint64_t)rr[g0 + j] & ridMask) : (uint64_t)rr[g0 + j];
+            const uint64_t row = rid - cols.offset;
+#pragma unroll
+            for (int c = 0; c < C; ++c) val[c][j] = __builtin_nontemporal_load(cols.col[c] + row * cols.stride[c]);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+          if (slot[j] != GJ_NONE) {
+            atomicAdd(&cnt[slot[j]], 1u);
+#pragma unroll
+            for (int c = 0; c < C; ++c) groupAggLds(&aggs[c * maxSlots + slot[j]], val[c][j], cols.agg[c]);
+          }
+        }
+      }
+    }
+    __syncthreads();
+
+    // ---- inner side: count and aggregates of the first slot of every inner tuple's key
+    for (uint32_t b0 = 0; b0 < nr; b0 += BATCH) {
+      if (nr > BATCH) groupLoad<LAYOUT, false, false>(a.R, a.Rhi, rb, nr, b0, a.fragShift, rv, nor);  // else in registers
+#pragma unroll
+      for (int k = 0; k < GJ_K; ++k) {
+        const uint32_t idx = b0 + k * GJ_T + t;
+        if (idx < nr) {
+          const K key = rv[k];
+          uint32_t h = groupHash<LAYOUT>(key, tbits);
+          while (table[h] != key) h = (h + 1) & mask;  // the key is in the table: this tuple inserted it
+          const uint32_t c0 = cnt[h];
+          if (c0) {
+            matches += c0;
+            atomicAdd(&accCount[rb + idx], c0);
+#pragma unroll
+            for (int c = 0; c < C; ++c)
+              groupAggGlobal(&accAgg[c * accSlots + rb + idx], aggs[c * maxSlots + h], cols.agg[c]);
+          }
+        }
+      }
+    }
+    __syncthreads();  // the next item clears the table
+  }
+  const unsigned long long total = blockReduceSum<GJ_T, unsigned long long>(matches, wsum);
+  if (t == 0 && total) atomicAdd(a.result, total);
+}
+
 // ------------------------------------------------------------------- units
 __global__ __launch_bounds__(GJ_T) void groupUnitLengthsKernel(BPArgs a, const MarkUnit *__restrict__ units,
                                                               const uint32_t *__restrict__ nUnitsPtr, uint32_t capacity,
@@ -368,6 +590,57 @@ __global__ __launch_bounds__(GJ_T) void groupEmitKernel(BPArgs a, const MarkUnit
   if (threadIdx.x == 0 && total) atomicAdd(a.result, total);
 }
 
+// groupEmitKernel<LAYOUT, true> with C aggregate words per row: W = 2 + C (4 to 6; one column takes groupEmitKernel).
+template <int LAYOUT, int C>
+__global__ __launch_bounds__(GJ_T) void groupEmitAggKernel(BPArgs a, const MarkUnit *__restrict__ units,
+                                                          const uint32_t *__restrict__ nUnitsPtr, uint32_t capacity,
+                                                          const uint32_t *__restrict__ accCount,
+                                                          const unsigned long long *__restrict__ accAgg,
+                                                          uint64_t accSlots,
+                                                          const unsigned long long *__restrict__ unitOffsets,
+                                                          unsigned long long *__restrict__ out, uint64_t outCapacity) {
+  constexpr uint32_t W = 2 + C;
+  __shared__ unsigned long long wsum[GJ_T / WAVE];
+  const uint32_t lane = threadIdx.x & (WAVE - 1);
+  const uint64_t ridMask = a.keyShift >= 64 ? ~0ull : ((1ull << a.keyShift) - 1);
+  const uint32_t nUnits = min(*nUnitsPtr, capacity);
+  const uint32_t wavesPerGrid = gridDim.x * (GJ_T / WAVE);
+  unsigned long long zeros = 0;
+  for (uint32_t u = blockIdx.x * (GJ_T / WAVE) + threadIdx.x / WAVE; u < nUnits; u += wavesPerGrid) {
+    uint64_t ub, ue;
+    unitRange(a, units[u], ub, ue);
+    const unsigned long long base = out ? unitOffsets[u] : 0ull;
+    for (uint64_t p0 = ub; p0 < ue; p0 += WAVE) {  // wave-uniform
+      const uint32_t m = (uint32_t)min((uint64_t)WAVE, ue - p0);
+      const bool valid = lane < m;
+      const uint32_t c = valid ? accCount[p0 + lane] : 1u;
+      zeros += c == 0;
+      if (!out) continue;
+      const unsigned long long row0 = base + (p0 - ub);  // the wave's first output row
+      const unsigned long long rid = valid ? markRid<LAYOUT>(a, p0 + lane, ridMask) : 0ull;
+      unsigned long long g[C];
+#pragma unroll
+      for (int j = 0; j < C; ++j) g[j] = valid ? accAgg[j * accSlots + p0 + lane] : 0ull;
+      // word q of the run (row q / W, column q % W) is stored by lane q % 64: consecutive 8-byte stores
+#pragma unroll
+      for (uint32_t k = 0; k < W; ++k) {
+        const uint32_t q = WAVE * k + lane, src = q / W, col = q - src * W;
+        const unsigned long long vr = __shfl(rid, src, WAVE);
+        const uint32_t vc = __shfl(c, src, WAVE);
+        unsigned long long v = col == 0 ? vr : (unsigned long long)vc;
+#pragma unroll
+        for (int j = 0; j < C; ++j) {
+          const unsigned long long vg = __shfl(g[j], src, WAVE);
+          if (col == 2u + j) v = vg;
+        }
+        if (src < m && row0 + src < outCapacity) out[row0 * W + q] = v;
+      }
+    }
+  }
+  const unsigned long long total = blockReduceSum<GJ_T, unsigned long long>(zeros, wsum);
+  if (threadIdx.x == 0 && total) atomicAdd(a.result, total);
+}
+
 // Small units are latency-bound per wave: the grid fills every CU with waves (as semi_join.hip).
 static uint32_t groupUnitGrid(uint32_t capacity) {
   const uint32_t perBlock = GJ_T / WAVE;
@@ -381,9 +654,9 @@ static BPArgs groupArgs(const BPArgs &args) {
   return a;
 }
 
-size_t bpGroupLdsBytes(const BPArgs &a, bool sum) {
-  if (groupDirect(a, sum)) return (size_t(4) << a.fragBits) + 64;
-  return groupTableBytes(a.rChunk, a.wide, sum);
+size_t bpGroupLdsBytes(const BPArgs &a, uint32_t columns) {
+  if (groupDirect(a, columns != 0)) return (size_t(4) << a.fragBits) + 64;
+  return groupTableBytes(a.rChunk, a.wide, columns);
 }
 
 void bpGroup(const BPArgs &args, const BPItem *items, const uint32_t *nItems, uint32_t capacity,
@@ -392,7 +665,7 @@ void bpGroup(const BPArgs &args, const BPItem *items, const uint32_t *nItems, ui
   if (capacity == 0) return;
   const BPArgs a = groupArgs(args);
   const bool sum = values != nullptr;
-  const size_t lds = bpGroupLdsBytes(a, sum);
+  const size_t lds = bpGroupLdsBytes(a, sum ? 1 : 0);
   HJ_CHECK(lds <= 160 * 1024, "bpGroup: LDS request %zu exceeds 160 KiB (rChunk=%u%s)", lds, a.rChunk,
            sum ? ", with a value column" : "");
   HJ_CHECK(!a.keyOnly, "bpGroup: key-only words carry no rid (group joins use rid-carrying layouts)");
@@ -465,6 +738,99 @@ void groupEmit(const BPArgs &args, const MarkUnit *units, const uint32_t *nUnits
       break;
   }
 #undef HJ_GJ_EMIT
+  HIP_CHECK_LAUNCH();
+}
+
+static void groupColumnsCheck(const GroupColumns &cols, const char *who) {
+  HJ_CHECK(cols.n >= 1 && cols.n <= GROUP_MAX_COLUMNS, "%s: %u value columns (1 to %u)", who, cols.n, GROUP_MAX_COLUMNS);
+  for (uint32_t c = 0; c < cols.n; ++c)
+    HJ_CHECK(cols.col[c] && cols.stride[c] >= 1 && cols.agg[c] <= GROUP_MAX,
+             "%s: column %u needs values, a stride >= 1 and an aggregate (sum, min, max)", who, c);
+}
+
+void groupAggFill(const GroupColumns &cols, unsigned long long *accAgg, uint64_t accSlots, hipStream_t s) {
+  if (accSlots == 0) return;
+  groupColumnsCheck(cols, "groupAggFill");
+  HJ_CHECK(accAgg, "groupAggFill: needs the accumulators");
+  const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(256 * 8, (accSlots + GJ_T - 1) / GJ_T));
+  hipLaunchKernelGGL(groupAggFillKernel, dim3(blocks), dim3(GJ_T), 0, s, cols, accAgg, accSlots);
+  HIP_CHECK_LAUNCH();
+}
+
+void bpGroupAgg(const BPArgs &args, const BPItem *items, const uint32_t *nItems, uint32_t capacity,
+                const GroupColumns &cols, uint32_t *accCount, unsigned long long *accAgg, uint64_t accSlots,
+                hipStream_t s) {
+  if (capacity == 0) return;
+  groupColumnsCheck(cols, "bpGroupAgg");
+  if (cols.n == 1 && cols.agg[0] == GROUP_SUM) {  // the single-column kernel (identity 0: the fill zeroed it)
+    bpGroup(args, items, nItems, capacity, cols.col[0], cols.offset, cols.stride[0], accCount, accAgg, s);
+    return;
+  }
+  const BPArgs a = groupArgs(args);
+  const size_t lds = bpGroupLdsBytes(a, cols.n);
+  HJ_CHECK(lds <= 160 * 1024, "bpGroupAgg: LDS request %zu exceeds 160 KiB (rChunk=%u, %u value columns)", lds, a.rChunk,
+           cols.n);
+  HJ_CHECK(!a.keyOnly, "bpGroupAgg: key-only words carry no rid (group joins use rid-carrying layouts)");
+  HJ_CHECK(!(a.split && a.wide), "bpGroupAgg: the split layout holds compressed tuples");
+  HJ_CHECK(!a.split || (a.Rhi && a.Shi), "bpGroupAgg: split layout without fragment columns");
+  HJ_CHECK(a.wide || a.fragShift >= 32, "bpGroupAgg: fragShift=%u < 32 (the rid field of a CompressedTuple is >= 32 bits)",
+           a.fragShift);
+  HJ_CHECK(a.result && accCount && accAgg, "bpGroupAgg: needs the pair counter and the accumulators");
+  const uint32_t perCu = (uint32_t)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / lds));
+  const uint32_t blocks = std::min<uint32_t>(capacity, 256 * perCu);
+#define HJ_GJ_AGG(LAYOUT, C)                                                                                        \
+  hipLaunchKernelGGL((bpGroupAggKernel<LAYOUT, C>), dim3(blocks), dim3(GJ_T), lds, s, a, items, nItems, capacity, cols, \
+                     accCount, accAgg, accSlots)
+#define HJ_GJ_AGG_C(LAYOUT)                   \
+  switch (cols.n) {                           \
+    case 1: HJ_GJ_AGG(LAYOUT, 1); break;      \
+    case 2: HJ_GJ_AGG(LAYOUT, 2); break;      \
+    case 3: HJ_GJ_AGG(LAYOUT, 3); break;      \
+    default: HJ_GJ_AGG(LAYOUT, 4); break;     \
+  }
+  switch (markLayout(a)) {
+    case MK_COMPRESSED: HJ_GJ_AGG_C(MK_COMPRESSED); break;
+    case MK_SPLIT: HJ_GJ_AGG_C(MK_SPLIT); break;
+    default: HJ_GJ_AGG_C(MK_WIDE); break;
+  }
+#undef HJ_GJ_AGG_C
+#undef HJ_GJ_AGG
+  HIP_CHECK_LAUNCH();
+}
+
+void groupEmitAgg(const BPArgs &args, const MarkUnit *units, const uint32_t *nUnits, uint32_t capacity,
+                  const uint32_t *accCount, const unsigned long long *accAgg, uint64_t accSlots, uint32_t columns,
+                  const unsigned long long *unitOffsets, unsigned long long *out, uint64_t outCapacity, hipStream_t s) {
+  if (capacity == 0) return;
+  HJ_CHECK(columns >= 1 && columns <= GROUP_MAX_COLUMNS, "groupEmitAgg: %u value columns (1 to %u)", columns,
+           GROUP_MAX_COLUMNS);
+  HJ_CHECK(accAgg, "groupEmitAgg: needs the aggregate accumulators");
+  if (columns == 1) {  // (rid, count, aggregate): the three-word rows of groupEmit
+    groupEmit(args, units, nUnits, capacity, accCount, accAgg, unitOffsets, out, outCapacity, s);
+    return;
+  }
+  const BPArgs a = groupArgs(args);
+  HJ_CHECK(!a.keyOnly, "groupEmitAgg: key-only words carry no rid");
+  HJ_CHECK(!(a.split && a.wide), "groupEmitAgg: the split layout holds compressed tuples");
+  HJ_CHECK(a.result && accCount, "groupEmitAgg: needs the empty-group counter and the count accumulators");
+  HJ_CHECK(!out || unitOffsets, "groupEmitAgg: rows need the unit offsets");
+  const dim3 grid(groupUnitGrid(capacity)), block(GJ_T);
+#define HJ_GJ_EMIT_AGG(LAYOUT, C)                                                                                      \
+  hipLaunchKernelGGL((groupEmitAggKernel<LAYOUT, C>), grid, block, 0, s, a, units, nUnits, capacity, accCount, accAgg, \
+                     accSlots, unitOffsets, out, outCapacity)
+#define HJ_GJ_EMIT_AGG_C(LAYOUT)                   \
+  switch (columns) {                               \
+    case 2: HJ_GJ_EMIT_AGG(LAYOUT, 2); break;      \
+    case 3: HJ_GJ_EMIT_AGG(LAYOUT, 3); break;      \
+    default: HJ_GJ_EMIT_AGG(LAYOUT, 4); break;     \
+  }
+  switch (markLayout(a)) {
+    case MK_COMPRESSED: HJ_GJ_EMIT_AGG_C(MK_COMPRESSED); break;
+    case MK_SPLIT: HJ_GJ_EMIT_AGG_C(MK_SPLIT); break;
+    default: HJ_GJ_EMIT_AGG_C(MK_WIDE); break;
+  }
+#undef HJ_GJ_EMIT_AGG_C
+#undef HJ_GJ_EMIT_AGG
   HIP_CHECK_LAUNCH();
 }
 

@@ -459,6 +459,25 @@ struct GroupValues {
   uint64_t rows = 0;
   uint64_t strideWords = 1;
 };
+// Outer value columns of a group join with aggregates (HashJoin::setGroupColumns):
+// n = 1 ... GROUP_MAX_COLUMNS columns, each a 1-D int64 view with its own base
+// pointer, positive element stride and aggregate; column c's value of rid r is
+// col[c][(r - offset) * stride[c]], rids [offset, offset + rows).  SUM wraps;
+// MIN and MAX compare as signed int64.  Passed to the kernels by value.
+constexpr uint32_t GROUP_MAX_COLUMNS = 4;
+enum GroupAgg : uint32_t { GROUP_SUM = 0, GROUP_MIN = 1, GROUP_MAX = 2 };
+struct GroupColumns {
+  const unsigned long long *col[GROUP_MAX_COLUMNS] = {nullptr, nullptr, nullptr, nullptr};
+  uint64_t stride[GROUP_MAX_COLUMNS] = {1, 1, 1, 1};
+  uint32_t agg[GROUP_MAX_COLUMNS] = {GROUP_SUM, GROUP_SUM, GROUP_SUM, GROUP_SUM};
+  uint32_t n = 0;
+  uint64_t offset = 0;
+  uint64_t rows = 0;
+};
+// What an aggregate of no value is: 0, INT64_MAX, INT64_MIN (the rows of empty groups carry it).
+HJ_HD unsigned long long groupAggIdentity(uint32_t agg) {
+  return agg == GROUP_MIN ? 0x7FFFFFFFFFFFFFFFull : agg == GROUP_MAX ? 0x8000000000000000ull : 0ull;
+}
 size_t bpLdsBytes(const BPArgs &a);
 // True when a count over the split layout uses the direct-addressed count
 // table (fragments <= 13 bits): its LDS table does not grow with the inner
@@ -569,19 +588,21 @@ void markPlacePairs(const BPArgs &a, const MarkUnit *units, const uint32_t *nUni
 // number of outer tuples with its key and, with a value column, the int64 sum
 // (wrapping) of values[(rid - ridOffset) * strideWords] over those tuples.
 // Slots of the largest hashed table of a launch, and its LDS bytes: 4- or
-// 8-byte keys, a u32 counter and (sum) a u64 accumulator per slot, plus the
+// 8-byte keys, a u32 counter and `columns` u64 accumulators per slot (0 = counts
+// only, 1 = a sum or one aggregate, up to GROUP_MAX_COLUMNS), plus the
 // reduction words.  Inline: the planner sizes rChunk with it (core::makePlan).
 HJ_HD uint64_t groupMaxSlots(uint32_t rChunk) {
   uint32_t b = 6;
   while ((uint64_t(1) << b) < 2ull * rChunk) ++b;
   return uint64_t(1) << b;
 }
-HJ_HD size_t groupTableBytes(uint32_t rChunk, bool wide, bool sum) {
-  return (size_t)(groupMaxSlots(rChunk) * ((wide ? 8 : 4) + 4 + (sum ? 8 : 0)) + 64);
+HJ_HD size_t groupTableBytes(uint32_t rChunk, bool wide, uint32_t columns) {
+  return (size_t)(groupMaxSlots(rChunk) * ((wide ? 8 : 4) + 4 + 8 * (size_t)columns) + 64);
 }
-// The LDS request of bpGroup (direct-addressed counts when there is no value
-// column and the fragments have at most 13 bits; the hashed table otherwise).
-size_t bpGroupLdsBytes(const BPArgs &a, bool sum);
+// The LDS request of bpGroup / bpGroupAgg (direct-addressed counts when there
+// is no value column and the fragments have at most 13 bits; the hashed table
+// with `columns` accumulators per slot otherwise).
+size_t bpGroupLdsBytes(const BPArgs &a, uint32_t columns);
 // Over the BPItem list of bpPlanCounts / bpEmit.  accCount (u32) and accSum
 // (u64, only read with values) are indexed by the position in the partitioned
 // inner buffer and zeroed by the caller; every item adds its outer chunk's
@@ -603,6 +624,22 @@ void groupUnitLengths(const BPArgs &a, const MarkUnit *units, const uint32_t *nU
 void groupEmit(const BPArgs &a, const MarkUnit *units, const uint32_t *nUnits, uint32_t capacity,
                const uint32_t *accCount, const unsigned long long *accSum, const unsigned long long *unitOffsets,
                unsigned long long *out, uint64_t outCapacity, hipStream_t s);
+
+// Group joins with aggregates: cols.n = 1 ... GROUP_MAX_COLUMNS value columns,
+// each summed (wrapping), or reduced to its signed minimum or maximum.
+// accCount as bpGroup; accAgg is column-major, accAgg[c * accSlots + position],
+// and must hold every column's identity before the launch (groupAggFill; the
+// accumulators of MIN and MAX cannot be cleared by a memset).  One column with
+// GROUP_SUM runs bpGroup itself.  An LDS request above 160 KiB is refused.
+void groupAggFill(const GroupColumns &cols, unsigned long long *accAgg, uint64_t accSlots, hipStream_t s);
+void bpGroupAgg(const BPArgs &a, const BPItem *items, const uint32_t *nItems, uint32_t capacity,
+                const GroupColumns &cols, uint32_t *accCount, unsigned long long *accAgg, uint64_t accSlots,
+                hipStream_t s);
+// Rows (rid, count, agg_0, ..., agg_{C-1}) of unit u's positions, W = 2 + C
+// words each, otherwise as groupEmit (one column runs groupEmit itself).
+void groupEmitAgg(const BPArgs &a, const MarkUnit *units, const uint32_t *nUnits, uint32_t capacity,
+                  const uint32_t *accCount, const unsigned long long *accAgg, uint64_t accSlots, uint32_t columns,
+                  const unsigned long long *unitOffsets, unsigned long long *out, uint64_t outCapacity, hipStream_t s);
 
 // Single-level counting join of unique inner keys (bitmap_join.hip): one
 // workgroup per network partition sets a 2^bits LDS bitmap from the inner

@@ -594,8 +594,9 @@ std::vector<uint64_t> HashJoin::workspaceParts() const {
                                          : recvTotal[0];
     const uint64_t units = P + recvTotal[0] / kernels::MARK_UNIT + 2;
     parts[0] += units * (sizeof(kernels::MarkUnit) + 4 + 8) + kernels::scanWorkspaceBytes(units) + 4096;
-    parts.push_back((slots + 2) * 12);
-    if (plan.materialize) parts.push_back((recvTotal[0] + 1) * 24);
+    // (with aggregated value columns: plan.groupColumns accumulators and row words instead of one)
+    parts.push_back((slots + 2) * (4 + 8ull * plan.groupColumns));
+    if (plan.materialize) parts.push_back((recvTotal[0] + 1) * (16 + 8ull * plan.groupColumns));
     return parts;
   }
   if (core::isOuterKind(plan.kind)) {
@@ -844,6 +845,45 @@ JoinResult HashJoin::joinGroup(const uint64_t *outerValues, uint64_t outerOffset
   return run();
 }
 
+void HashJoin::setGroupColumns(const kernels::GroupColumns &c) {
+  JOIN_ASSERT(plan.kind == core::JoinKind::Group, "HashJoin",
+              "value columns to aggregate (join_group_agg) need JoinConfig.kind = group, this join has kind = %s",
+              core::joinKindName(plan.kind));
+  JOIN_ASSERT(ctx->comm()->size() == 1, "HashJoin",
+              "join_group_agg: value columns of a kind = group join need a single rank (world size %u): the values of "
+              "outer tuples received from other ranks live on those ranks; without value columns every rank counts",
+              ctx->comm()->size());
+  JOIN_ASSERT(passes == 1, "HashJoin",
+              "join_group_agg: value columns cannot be combined with a capacity spill (%u passes)", passes);
+  JOIN_ASSERT(c.n >= 1 && c.n <= kernels::GROUP_MAX_COLUMNS, "HashJoin",
+              "join_group_agg: %u value columns; a group join aggregates 1 to %u", c.n, kernels::GROUP_MAX_COLUMNS);
+  JOIN_ASSERT(c.n <= plan.groupColumns, "HashJoin",
+              "join_group_agg: %u value columns, but the plan sized its LDS tables for JoinConfig.groupColumns "
+              "(group_columns) = %u; set group_columns to the number of columns before constructing the join",
+              c.n, plan.groupColumns);
+  for (uint32_t i = 0; i < c.n; ++i) {
+    JOIN_ASSERT(c.col[i] && c.stride[i] >= 1, "HashJoin", "join_group_agg: column %u needs values and a positive stride", i);
+    JOIN_ASSERT(c.agg[i] <= kernels::GROUP_MAX, "HashJoin", "join_group_agg: column %u has no aggregate %u", i, c.agg[i]);
+  }
+  JOIN_ASSERT(ridLo[1] > ridHi[1] || (ridLo[1] >= c.offset && ridHi[1] - c.offset < c.rows), "HashJoin",
+              "join_group_agg: outer values [%lu, %lu) do not cover this rank's outer rids [%lu, %lu]",
+              (unsigned long)c.offset, (unsigned long)(c.offset + c.rows), (unsigned long)ridLo[1],
+              (unsigned long)ridHi[1]);
+  groupColumns = c;
+  hasGroupColumns = true;
+}
+
+JoinResult HashJoin::joinGroupAgg(kernels::GroupColumns columns, uint64_t outerOffset, uint64_t outerGlobal) {
+  columns.offset = outerOffset;
+  columns.rows = outerGlobal;
+  setGroupColumns(columns);
+  struct Clear {
+    HashJoin &j;
+    ~Clear() { j.clearGroupColumns(); }
+  } clear{*this};
+  return run();
+}
+
 void HashJoin::join() {
   run();
   RESULT_COUNTER = result.localMatches;
@@ -1002,7 +1042,20 @@ JoinResult HashJoin::runImpl() {
 
   // --------------------------------------------- local pass and build/probe
   LocalPhase local(env, localOverflowed, hasSink && (canFuseRows() || canFuseKindRows()) ? &sink : nullptr);
-  if (hasGroupValues && plan.kind == core::JoinKind::Group) local.setGroupValues(&groupValues);
+  kernels::GroupValues oneSum;  // a single SUM column takes the single-column kernels
+  if (hasGroupColumns && plan.kind == core::JoinKind::Group) {
+    if (groupColumns.n == 1 && groupColumns.agg[0] == kernels::GROUP_SUM) {
+      oneSum.values = reinterpret_cast<const uint64_t *>(groupColumns.col[0]);
+      oneSum.offset = groupColumns.offset;
+      oneSum.rows = groupColumns.rows;
+      oneSum.strideWords = groupColumns.stride[0];
+      local.setGroupValues(&oneSum);
+    } else {
+      local.setGroupColumns(&groupColumns);
+    }
+  } else if (hasGroupValues && plan.kind == core::JoinKind::Group) {
+    local.setGroupValues(&groupValues);
+  }
   local.run(run, result);
   const uint64_t t4 = nowUs();
   ctx->timeline().resolve();  // every stream was synchronised above

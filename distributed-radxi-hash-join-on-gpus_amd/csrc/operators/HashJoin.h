@@ -43,6 +43,7 @@ struct JoinResult {
   uint64_t matchedPairs = 0, unmatchedInner = 0, unmatchedOuter = 0;
   uint64_t outputGroups = 0;       // kind Group, materialize: rows written on this rank
   bool groupSums = false;          // kind Group: the rows carry a sum (3 words, else 2)
+  uint32_t groupColumns = 0;       // kind Group: aggregate words per row (0 count only, 1 joinGroup; rows are 2 + this)
   bool rowsFused = false;          // materialize: whole rows went to the RowSink (no pair array)
   uint32_t reruns = 0;             // build/probe re-launches after an item/output overflow
   double joinMs = 0;               // host wall: histogram start -> local result available
@@ -112,8 +113,8 @@ class HashJoin {
   const uint64_t *getOutputRids() const { return outputRids; }
   bool outputRidsValid() const;
   // kind Group with materialize: the rows of the last run()
-  // (lastResult().outputGroups of them, any order; 2 words (rid, count) or,
-  // when it summed a value column, 3 words (rid, count, sum)), in the engine's
+  // (lastResult().outputGroups of them, any order; 2 + lastResult().groupColumns
+  // words: (rid, count), (rid, count, sum) or (rid, count, agg_0, ...)), in the engine's
   // workspace under the same validity rule as getOutput().
   const uint64_t *getOutputGroups() const { return outputGroups; }
   bool outputGroupsValid() const;
@@ -123,6 +124,14 @@ class HashJoin {
   void setGroupValues(const kernels::GroupValues &v);
   void clearGroupValues() { hasGroupValues = false; }
   JoinResult joinGroup(const uint64_t *outerValues, uint64_t outerOffset, uint64_t outerGlobal, uint64_t strideWords);
+  // kind Group: while set, run() aggregates cols.n (at most the plan's
+  // groupColumns) outer value columns per group, each by its own SUM, MIN or
+  // MAX; the rows are (rid, count, agg_0, ...).  The same checks as
+  // setGroupValues, for every column.  One SUM column runs as setGroupValues.
+  // joinGroupAgg = set (offset and rows from its arguments), run, clear.
+  void setGroupColumns(const kernels::GroupColumns &cols);
+  void clearGroupColumns() { hasGroupColumns = false; }
+  JoinResult joinGroupAgg(kernels::GroupColumns columns, uint64_t outerOffset, uint64_t outerGlobal);
   // Fused materialization: while a sink is set, a device join at N = 1 over
   // the split layout writes whole output rows (LateMaterialization's layout)
   // from its materialize pass instead of pairs.  canFuseRows() says whether
@@ -210,6 +219,8 @@ class HashJoin {
   const uint64_t *outputGroups = nullptr;
   kernels::GroupValues groupValues;
   bool hasGroupValues = false;
+  kernels::GroupColumns groupColumns;
+  bool hasGroupColumns = false;
   // Capacity spill (planPasses / runPasses): pass count, this rank's and the
   // global tuple counts per pass, the pass buffers (one inner and one outer
   // pass at a time) and the plan's global key / rid bounds.

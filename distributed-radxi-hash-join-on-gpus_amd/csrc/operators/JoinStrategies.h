@@ -133,6 +133,8 @@ class LocalPhase {
   std::vector<std::unique_ptr<tasks::BuildProbe>> &buildProbes() { return bps; }
   // kind Group: the outer value column to sum (null: counts only).
   void setGroupValues(const kernels::GroupValues *v) { groupValues = v; }
+  // kind Group: the outer value columns to aggregate (null: none).
+  void setGroupColumns(const kernels::GroupColumns *c) { groupColumns = c; }
   void release() {
     bps.clear();
     outerViews.clear();
@@ -144,6 +146,7 @@ class LocalPhase {
   bool &localOverflowed;
   const kernels::RowSink *sink;  // fused row output (N = 1 materializing joins), or null
   const kernels::GroupValues *groupValues = nullptr;
+  const kernels::GroupColumns *groupColumns = nullptr;
   std::vector<std::unique_ptr<tasks::BuildProbe>> bps;
   std::vector<std::unique_ptr<data::Window>> outerViews;
 };

@@ -11,6 +11,8 @@ host twins (CPU tensors).  Tuples are int64 tensors of shape [n, 2] holding
     semi_join_rows(R, S, S_rows), anti_join_rows(R, S, S_rows)            # [m, 5]: outer rid + its payload row
     full_outer_join_rows(R, S, R_rows, S_rows)                            # [m, 10]: rids + both rows, NULL_RID-padded
     group_join_count(R, S), group_join_sum(R, S, values)   # per inner tuple: [|R|, 2] (rid, count) / [|R|, 3] (+ sum)
+    group_join_agg(R, S, [a, b, b], ["sum", "min", "max"])  # [|R|, 2 + C]: (rid, count, agg_0, ...), C = 1 ... 4 columns
+                                                           # (AVG is sum / count on the caller's side)
 """
 from __future__ import annotations
 
@@ -103,6 +105,18 @@ def build_probe_group(R, S, part_r, part_s, frag_shift: int, key_shift: int, wid
     of R)."""
     return _C().ops.build_probe_group(R, S, part_r, part_s, frag_shift, key_shift, wide, r_chunk, s_chunk, values,
                                       rid_offset)
+
+
+def build_probe_group_agg(R, S, part_r, part_s, frag_shift: int, key_shift: int, wide=False, r_chunk=4096,
+                          s_chunk=65536, columns=(), aggs=(), rid_offset=0) -> dict:
+    """Group join with aggregates over matching partitions: ``columns`` are 1 ... 4 1-D int64 tensors (any positive
+    element stride each, ``column[rid - rid_offset]`` the value of outer tuple ``rid``), ``aggs`` one of ``"sum"``
+    (int64, wraps), ``"min"``, ``"max"`` (signed) per column.  ``rows`` (int64 ``[|R|, 2 + C]`` of (inner rid, count,
+    agg_0, ...); a tuple without a partner has count 0 and each aggregate's identity: 0, INT64_MAX, INT64_MIN),
+    ``matched_pairs``, ``unmatched_inner`` and the raw accumulators ``counts`` (``[|R|]``) and ``aggs``
+    (``[C, |R|]``), by position of R."""
+    return _C().ops.build_probe_group_agg(R, S, part_r, part_s, frag_shift, key_shift, wide, r_chunk, s_chunk,
+                                          list(columns), [str(a) for a in aggs], rid_offset)
 
 
 def build_probe_outer_rows(R, S, part_r, part_s, frag_shift: int, key_shift: int, wide=False, r_chunk=4096,
@@ -268,6 +282,28 @@ def group_join_sum(inner: torch.Tensor, outer: torch.Tensor, values: torch.Tenso
     ``values[rid - rid_offset]`` over the outer tuples with its key.  ``values`` is a 1-D int64 tensor of any
     positive element stride (a column view such as ``S_rows[:, 2]`` is read in place)."""
     return _group_join(inner, outer, values, rid_offset, config)
+
+
+def group_join_agg(inner: torch.Tensor, outer: torch.Tensor, columns, aggs, rid_offset: int = 0,
+                   config=None) -> torch.Tensor:
+    """int64 [|inner|, 2 + C]: ``(inner rid, count, agg_0, ..., agg_{C-1})`` per inner tuple over the outer tuples
+    with its key.  ``columns``: C = 1 ... 4 1-D int64 tensors with ``column[rid - rid_offset]`` the value of outer
+    tuple ``rid`` (views such as ``S_rows[:, 1]`` are read in place; the same view may come twice); ``aggs``: one
+    of ``"sum"`` (wraps), ``"min"``, ``"max"`` (signed) per column.  A tuple without a partner has count 0 and each
+    aggregate's identity (0, INT64_MAX, INT64_MIN).  AVG is ``sum / count`` on the caller's side."""
+    C = _C()
+    cfg = config or C.JoinConfig()
+    cfg.kind = C.JoinKind.GROUP
+    cfg.materialize = True
+    cfg.group_columns = max(1, min(len(columns), 4))  # (more than four: refused by join_group_agg)
+    on_dev = inner.is_cuda
+    ctx = C.ExecContext("device" if on_dev else "host", (inner.device.index or 0) if on_dev else -1,
+                        C.LocalCommunicator())
+    R = C.Relation.from_tensor(inner.contiguous(), inner.shape[0])
+    S = C.Relation.from_tensor(outer.contiguous(), outer.shape[0])
+    j = C.HashJoin(R, S, ctx, cfg)
+    _, rows = j.join_group_agg(ctx, list(columns), [str(a) for a in aggs], rid_offset, outer.shape[0])
+    return rows
 
 
 def _kind_join_rows(inner, outer, kind: str, inner_rows, outer_rows, rid_offset: int, config=None) -> torch.Tensor:

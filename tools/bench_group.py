@@ -17,11 +17,20 @@ iterations:
      place of counters).
   c  a materializing GROUP join without a value column.
   d  a materializing GROUP join with a value column (join_group).
+  e  three join_group runs, one per value column: today's engine route for the
+     sums of three columns (join_ms and build/probe spans added up).
+  f  one GROUP join over the three columns, [sum, sum, sum] (join_group_agg).
+  g  one GROUP join over the three columns, [sum, min, max] (join_group_agg),
+     next to a's pair list reduced by torch: gathers of the three columns,
+     index_add_ and scatter_reduce_ amin / amax (timed with device events).
+  h1 ... h4  join_group_agg over C = 1 ... 4 columns ([min], [min, sum], ...):
+     the build/probe span per column count, next to d's.
 
 Every result is checked against oracle counts (sorted outer keys, searchsorted
-of the inner keys) and sums (wrapping prefix sums of the values in outer key
-order).  The last line compares the medians: c and d must lie below a by more
-than a's own min-to-max spread; c / b is reported.
+of the inner keys), sums (wrapping prefix sums of the values in outer key
+order) and minima / maxima (scatter_reduce_ over the matching outer tuples).
+The last lines compare the medians: c and d must lie below a by more than a's
+own min-to-max spread; c / b, f / e and g against a's torch route are reported.
 """
 import argparse
 import json
@@ -60,6 +69,10 @@ def main():
     R.generate(inner, 0)
     S.generate(outer, 0)
     values = torch.randint(-2**40, 2**40, (G_S,), device="cuda", generator=torch.Generator("cuda").manual_seed(9))
+    # Two more value columns: with `values` the columns 1, 2, 3 of one [n, 4] payload tensor, read in place.
+    payload = torch.randint(-2**40, 2**40, (G_S, 4), device="cuda", generator=torch.Generator("cuda").manual_seed(10))
+    payload[:, 1] = values
+    cols = [payload[:, 1], payload[:, 2], payload[:, 3]]
 
     # ---- oracle, by inner rid (rids are 0 .. G_R - 1)
     Rt, St = R.to_tensor(), S.to_tensor()
@@ -72,7 +85,28 @@ def main():
     want_counts[Rt[:, 1]] = hi - lo
     want_sums[Rt[:, 1]] = prefix[hi] - prefix[lo]  # int64 wraps both ways
     pairs_total, empty = int(want_counts.sum()), int((want_counts == 0).sum())
-    del sk, order, lo, hi, prefix, Rt, St
+    del prefix
+
+    def want_agg(col, how):  # by inner rid, from the outer tuples in key order
+        v = col[St[:, 1][order]]
+        if how == "sum":
+            p = torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda"), torch.cumsum(v, 0)])
+            per_pos = p[hi] - p[lo]
+        else:
+            seg = torch.repeat_interleave(torch.arange(G_R, device="cuda"), hi - lo)  # inner position of every pair
+            src = v[torch.repeat_interleave(lo, hi - lo) + torch.arange(seg.numel(), device="cuda") -
+                    torch.repeat_interleave(torch.cumsum(hi - lo, 0) - (hi - lo), hi - lo)]
+            ident = 2**63 - 1 if how == "min" else -2**63
+            per_pos = torch.full((G_R,), ident, dtype=torch.int64, device="cuda").scatter_reduce_(
+                0, seg, src, "amin" if how == "min" else "amax", include_self=True)
+        out = torch.empty(G_R, dtype=torch.int64, device="cuda")
+        out[Rt[:, 1]] = per_pos
+        return out
+
+    want = {(c, how): want_agg(cols[c], how) for c, how in ((0, "sum"), (1, "sum"), (2, "sum"), (0, "min"), (1, "min"),
+                                                             (2, "max"))}
+    assert torch.equal(want[(0, "sum")], want_sums)
+    del sk, order, lo, hi, Rt, St
     torch.cuda.empty_cache()
 
     def join(kind, materialize):
@@ -119,11 +153,32 @@ def main():
             torch_ms["count"].append(ev[0].elapsed_time(ev[1]))
             torch_ms["sum"].append(ev[1].elapsed_time(ev[2]))
     assert torch.equal(counts, want_counts) and torch.equal(sums, want_sums)
+    # the same pair list reduced to [sum, min, max] of the three columns (configuration g's baseline)
+    torch_agg_ms = []
+    for it in range(a.warmup + a.steps):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        m = pairs[:, 1] != hpcjoin.NULL_RID
+        rid, srid = pairs[:, 0][m], pairs[:, 1][m]
+        counts = torch.bincount(rid, minlength=G_R)
+        t_sum = torch.zeros(G_R, dtype=torch.int64, device="cuda").index_add_(0, rid, cols[0][srid])
+        t_min = torch.full((G_R,), 2**63 - 1, dtype=torch.int64, device="cuda").scatter_reduce_(
+            0, rid, cols[1][srid], "amin", include_self=True)
+        t_max = torch.full((G_R,), -2**63, dtype=torch.int64, device="cuda").scatter_reduce_(
+            0, rid, cols[2][srid], "amax", include_self=True)
+        ev[1].record()
+        torch.cuda.synchronize()
+        if it >= a.warmup:
+            torch_agg_ms.append(ev[0].elapsed_time(ev[1]))
+    assert torch.equal(t_sum, want[(0, "sum")]) and torch.equal(t_min, want[(1, "min")]) and torch.equal(t_max, want[(2, "max")])
+    del t_sum, t_min, t_max
     total = {k: [r["join_ms"] + t for r, t in zip(runs, torch_ms[k])] for k in ("count", "sum")}
     total["sum"] = [x + c for x, c in zip(total["sum"], torch_ms["count"])]  # the mask and rids are shared
+    total["agg"] = [r["join_ms"] + t for r, t in zip(runs, torch_agg_ms)]
     lines["a"] = report("a", "LEFT_OUTER materialize + torch bincount / index_add_", j, runs, {
         "rows": int(pairs.shape[0]), "torch_count_ms": _spread(torch_ms["count"]), "torch_sum_ms": _spread(torch_ms["sum"]),
-        "total_count_ms": _spread(total["count"]), "total_sum_ms": _spread(total["sum"])})
+        "total_count_ms": _spread(total["count"]), "total_sum_ms": _spread(total["sum"]),
+        "torch_sum_min_max_ms": _spread(torch_agg_ms), "total_sum_min_max_ms": _spread(total["agg"])})
     del j, pairs, m, rid, srid, counts, sums
     ctx.trim_workspace()
     torch.cuda.empty_cache()
@@ -158,6 +213,66 @@ def main():
     rows = rows.cuda()
     assert rows.shape == (G_R, 3) and torch.equal(by_rid(rows, 1), want_counts) and torch.equal(by_rid(rows, 2), want_sums)
     lines["d"] = report("d", "GROUP materialize, counts and sums (join_group)", j, runs, {"rows": G_R})
+
+    del rows, j
+    ctx.trim_workspace()
+
+    # ---- e: the sums of three columns today: one join_group per column
+    j = join("GROUP", True)
+    runs = []
+    for it in range(a.warmup + a.steps):
+        step = []
+        for c in range(3):
+            res, rows = j.join_group(ctx, cols[c], 0, G_S)
+            step.append(res)
+            if it == a.warmup + a.steps - 1:
+                assert torch.equal(by_rid(rows.cuda(), 2), want[(c, "sum")])
+        if it >= a.warmup:
+            merged = dict(step[-1])
+            merged["join_ms"] = sum(r["join_ms"] for r in step)
+            merged["dev_build_probe_ms"] = sum(r["dev_build_probe_ms"] for r in step)
+            runs.append(merged)
+    lines["e"] = report("e", "GROUP, three join_group runs (one per column)", j, runs, {"rows": G_R})
+    del j, rows
+    ctx.trim_workspace()
+
+    def agg_join(name, what, columns, aggs, wanted):
+        cfg = C.JoinConfig()
+        cfg.kind = C.JoinKind.GROUP
+        cfg.materialize = True
+        cfg.group_columns = len(columns)
+        jj = C.HashJoin(R, S, ctx, cfg)
+        rr = []
+        for it in range(a.warmup + a.steps):
+            res, rows = jj.join_group_agg(ctx, columns, aggs, 0, G_S)
+            if it >= a.warmup:
+                rr.append(res)
+        rows = rows.cuda()
+        assert rows.shape == (G_R, 2 + len(columns)) and torch.equal(by_rid(rows, 1), want_counts)
+        for k, w in enumerate(wanted):
+            assert torch.equal(by_rid(rows, 2 + k), want[w]), (name, k)
+        lines[name] = report(name, what, jj, rr, {"rows": G_R, "columns": len(columns), "aggs": aggs})
+        del rows, jj
+        ctx.trim_workspace()
+
+    agg_join("f", "GROUP join_group_agg [sum, sum, sum]", cols, ["sum", "sum", "sum"], [(0, "sum"), (1, "sum"), (2, "sum")])
+    agg_join("g", "GROUP join_group_agg [sum, min, max]", cols, ["sum", "min", "max"], [(0, "sum"), (1, "min"), (2, "max")])
+    agg_join("h1", "GROUP join_group_agg [min]", cols[:1], ["min"], [(0, "min")])
+    agg_join("h2", "GROUP join_group_agg [min, sum]", cols[:2], ["min", "sum"], [(0, "min"), (1, "sum")])
+    agg_join("h3", "GROUP join_group_agg [min, sum, max]", cols, ["min", "sum", "max"], [(0, "min"), (1, "sum"), (2, "max")])
+    agg_join("h4", "GROUP join_group_agg [min, sum, max, sum]", cols + [cols[0]], ["min", "sum", "max", "sum"],
+             [(0, "min"), (1, "sum"), (2, "max"), (0, "sum")])
+    a_agg = lines["a"]["total_sum_min_max_ms"]
+    print(json.dumps({
+        "workload": wl.name, "comparison": "aggregated columns, join_ms medians",
+        "e_three_join_group": lines["e"]["join_ms"]["median"], "f_sum_sum_sum": lines["f"]["join_ms"]["median"],
+        "e_over_f": round(lines["e"]["join_ms"]["median"] / lines["f"]["join_ms"]["median"], 3),
+        "e_over_f_build_probe": round(lines["e"]["dev_build_probe_ms"]["median"] / lines["f"]["dev_build_probe_ms"]["median"], 3),
+        "a_sum_min_max": a_agg, "g_sum_min_max": lines["g"]["join_ms"]["median"],
+        "a_over_g": round(a_agg["median"] / lines["g"]["join_ms"]["median"], 3),
+        "build_probe_ms_by_columns": {"join_group": lines["d"]["dev_build_probe_ms"]["median"],
+                                      **{str(k): lines["h%d" % k]["dev_build_probe_ms"]["median"] for k in (1, 2, 3, 4)}},
+        "checked": "counts, sums, minima and maxima equal the oracle"}), flush=True)
 
     a_count, a_sum = lines["a"]["total_count_ms"], lines["a"]["total_sum_ms"]
     c_med, d_med, b_med = (lines[k]["join_ms"]["median"] for k in ("c", "d", "b"))
