@@ -8,6 +8,7 @@
 //               [--chunks C] [--net-bits B] [--local-bits B] [--materialize] [--wide]
 //               [--round-robin] [--perf-dir DIR] [--kind inner|semi|anti|left|right|full|group]
 //               [--inner-domain D] [--outer-domain D] [--outer-key-offset K] [--semi-bitmap]
+//               [--packed-fragments auto|on|off]
 // --semi-bitmap: JoinConfig::semiBitmap (--kind semi|anti on one rank: the
 // set-semantics bitmap plan; the [INFO] plan line then says bitmapSet).
 // --kind semi|anti: `matches` is the number of outer tuples with / without an
@@ -81,6 +82,16 @@ int main(int argc, char **argv) {
     else if (a == "--round-robin") cfg.assignment = core::AssignmentPolicy::RoundRobin;
     else if (a == "--two-level-only") cfg.bitmapJoin = false;  // no single-level bitmap join (N == 1)
     else if (a == "--semi-bitmap") cfg.semiBitmap = true;  // --kind semi|anti at N == 1: the set bitmap plan
+    else if (a == "--packed-fragments") {  // JoinConfig::packedFragments: the [INFO] plan line then says packed
+      const std::string k = next();
+      if (k == "auto") cfg.packedFragments = core::PlanChoice::Auto;
+      else if (k == "on") cfg.packedFragments = core::PlanChoice::On;
+      else if (k == "off") cfg.packedFragments = core::PlanChoice::Off;
+      else {
+        std::fprintf(stderr, "unknown --packed-fragments %s (auto|on|off)\n", k.c_str());
+        return 2;
+      }
+    }
     else if (a == "--perf-dir") perfDir = next();
     else if (a == "--inner-domain") innerDomain = std::stoull(next());
     else if (a == "--outer-domain") outerDomain = std::stoull(next());

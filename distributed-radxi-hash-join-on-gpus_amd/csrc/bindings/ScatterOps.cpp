@@ -74,8 +74,13 @@ py::dict opNetScatterSlices(const at::Tensor &tuples, int64_t bits, const std::s
                   tuples.is_contiguous(),
               "net_scatter_slices: tuples must be a contiguous device int64 tensor of shape [n, 2] (key, rid)");
   const bool compressed = format == "compressed", keyOnly = format == "key_only", frag = format == "frag",
-             wide = format == "wide";
-  TORCH_CHECK(compressed || keyOnly || frag || wide, "net_scatter_slices: format ", format);
+             wide = format == "wide", packed = format == "frag_packed";
+  TORCH_CHECK(compressed || keyOnly || frag || wide || packed, "net_scatter_slices: format ", format);
+  // Packed fragment words (kernels.h, PK_*): the window and the slice tables count u64 words.
+  TORCH_CHECK(!packed || (bits <= kernels::PK_MAX_PART_BITS && !unbounded && shrink % kernels::PK_CHUNK_WORDS == 0 &&
+                          (roundLpArg == 0 || roundLpArg >= 3)),
+              "net_scatter_slices: frag_packed takes at most ", kernels::PK_MAX_PART_BITS,
+              " bits, bounded slices, shrink in whole chunks and round pieces of whole chunks");
   TORCH_CHECK(bits >= 1 && bits <= kernels::MAX_PART_BITS, "net_scatter_slices: bits=", bits);
   TORCH_CHECK(range == 0 || frag, "net_scatter_slices: range passes scatter fragments");
   TORCH_CHECK(roundLpArg == 0 || (!wide && range == 0), "net_scatter_slices: round slices need a whole-range, ",
@@ -98,7 +103,9 @@ py::dict opNetScatterSlices(const at::Tensor &tuples, int64_t bits, const std::s
   const uint32_t stride = kernels::sampleStrideFor(geom, n, F, (uint32_t)sampleStride);
   const kernels::SampleScale sc = kernels::sampleScale(geom, n, stride, stride == 1);
   const uint32_t roundLp = kernels::roundLpFor((uint32_t)roundLpArg, frag ? 4 : 8);
-  const uint64_t capacity = kernels::sampledWindowCapacity(sc, F, roundLp);
+  const uint32_t tailWords = packed ? kernels::packedTailWords(geom) : 0;
+  const uint64_t capacity = packed ? kernels::sampledPackedWindowCapacity(sc, F, roundLp, tailWords)
+                                   : kernels::sampledWindowCapacity(sc, F, roundLp);
 
   // sample(): sampled totals, or the exact histogram.
   at::Tensor totals = at::zeros({(int64_t)G * F}, on(tuples, at::kLong));
@@ -129,6 +136,8 @@ py::dict opNetScatterSlices(const at::Tensor &tuples, int64_t bits, const std::s
   at::Tensor capacityUsed = at::zeros({1}, on(tuples, at::kLong));
   kernels::LayoutInput lin{ptr<uint64_t>(totals), sc, base, base + per, base + 2 * per,
                            ptr<unsigned long long>(capacityUsed)};
+  lin.packed = packed;
+  lin.packedTail = tailWords;
   if (roundLp) {
     uint32_t lns = 0;
     while ((1u << lns) < G * F) ++lns;
@@ -174,7 +183,11 @@ py::dict opNetScatterSlices(const at::Tensor &tuples, int64_t bits, const std::s
   const int nm = narrow ? 1 : 0;
   void *gcur = base + per;
   const void *gend = unbounded ? nullptr : base + 2 * per;
-  if (frag && range)
+  at::Tensor wideFlag = at::zeros({1}, on(tuples, at::kLong));
+  if (packed)
+    kernels::netScatterFragPacked(in, n, (uint32_t)bits, geom, gcur, ptr<uint64_t>(window), st, mix, gend, narrow,
+                                  roundMeta, ptr<unsigned long long>(wideFlag));
+  else if (frag && range)
     kernels::netScatterFragRange(in, n, (uint32_t)bits, geom, gcur, ptr<uint32_t>(window), st, (uint32_t)keyBits, mix,
                                  gend, narrow, (uint32_t)dLo, (uint32_t)range);
   else if (frag)
@@ -200,6 +213,7 @@ py::dict opNetScatterSlices(const at::Tensor &tuples, int64_t bits, const std::s
   d["tiles_per_block"] = geom.tilesPerBlock;
   d["sample_stride"] = stride;
   d["narrow"] = narrow;
+  if (packed) d["wide_flag"] = (uint64_t)wideFlag.cpu()[0].item<int64_t>();  // waves that met a fragment above 20 bits
   return d;
 }
 
@@ -379,15 +393,55 @@ at::Tensor opKeyMix(const at::Tensor &keys, int64_t bits) {
   return out;
 }
 
+// Host twins of the packed fragment word (kernels.h, PK_*; kernels::packFragments).
+at::Tensor opPackFragments(const at::Tensor &frags, const at::Tensor &counts) {
+  TORCH_CHECK(!frags.is_cuda() && frags.scalar_type() == at::kLong && frags.dim() == 2 &&
+                  frags.size(1) == kernels::PK_WORD_FRAGS && !counts.is_cuda() && counts.scalar_type() == at::kLong &&
+                  counts.dim() == 1 && counts.size(0) == frags.size(0),
+              "pack_fragments: host int64 fragments [m, 3] and counts [m]");
+  at::Tensor f = frags.contiguous(), c = counts.contiguous(), out = at::empty({f.size(0)}, f.options());
+  const int64_t *pf = f.data_ptr<int64_t>(), *pc = c.data_ptr<int64_t>();
+  uint64_t *po = ptr<uint64_t>(out);
+  for (int64_t i = 0; i < f.size(0); ++i) {
+    TORCH_CHECK(pc[i] >= 0 && pc[i] <= (int64_t)kernels::PK_WORD_FRAGS, "pack_fragments: count ", pc[i]);
+    for (int e = 0; e < 3; ++e)
+      TORCH_CHECK(pf[3 * i + e] >= 0 && pf[3 * i + e] < (int64_t)1 << kernels::PK_FRAG_BITS,
+                  "pack_fragments: fragment ", pf[3 * i + e], " does not fit ", kernels::PK_FRAG_BITS, " bits");
+    po[i] = kernels::packFragments((uint32_t)pf[3 * i], (uint32_t)pf[3 * i + 1], (uint32_t)pf[3 * i + 2],
+                                   (uint32_t)pc[i]);
+  }
+  return out;
+}
+
+py::tuple opUnpackFragments(const at::Tensor &words) {
+  TORCH_CHECK(!words.is_cuda() && words.scalar_type() == at::kLong && words.dim() == 1,
+              "unpack_fragments: a host int64 tensor of words");
+  at::Tensor w = words.contiguous();
+  at::Tensor frags = at::empty({w.size(0), (int64_t)kernels::PK_WORD_FRAGS}, w.options());
+  at::Tensor counts = at::empty({w.size(0)}, w.options());
+  const uint64_t *pw = ptr<const uint64_t>(w);
+  int64_t *pf = frags.data_ptr<int64_t>(), *pc = counts.data_ptr<int64_t>();
+  const uint64_t m = (1ull << kernels::PK_FRAG_BITS) - 1;
+  for (int64_t i = 0; i < w.size(0); ++i) {
+    for (uint32_t e = 0; e < kernels::PK_WORD_FRAGS; ++e)
+      pf[3 * i + e] = (int64_t)((pw[i] >> (kernels::PK_FRAG_BITS * e)) & m);
+    pc[i] = (int64_t)(pw[i] >> 60);
+  }
+  return py::make_tuple(frags, counts);
+}
+
 }  // namespace
 
 void bindScatterOps(py::module_ &ops) {
+  ops.def("pack_fragments", &opPackFragments, py::arg("frags"), py::arg("counts"),
+          "Packed fragment words (three 20-bit fragments, count in bits 60-63) from [m, 3] fragments and [m] counts");
+  ops.def("unpack_fragments", &opUnpackFragments, py::arg("words"), "(fragments [m, 3], counts [m]) of packed words");
   ops.def("net_scatter_slices", &opNetScatterSlices, py::arg("tuples"), py::arg("bits"), py::arg("format"),
           py::arg("key_shift") = 32, py::arg("key_bits") = 64, py::arg("mix_bits") = 0, py::arg("narrow") = -1,
           py::arg("max_blocks") = 2048, py::arg("sample_stride") = 1, py::arg("round_lp") = 0, py::arg("d_lo") = 0,
           py::arg("range") = 0, py::arg("shrink") = 0, py::arg("guard") = 0, py::arg("unbounded") = false,
           "The sampled network pass of one relation (layout + bounded claim scatter) into a sentinel-filled window; "
-          "format = compressed | key_only | frag | wide");
+          "format = compressed | key_only | frag | wide | frag_packed (window and slice tables in packed u64 words)");
   ops.def("local_scatter_slices", &opLocalScatterSlices, py::arg("window"), py::arg("runs"), py::arg("owned"),
           py::arg("shift"), py::arg("bits"), py::arg("mode"), py::arg("round_map") = std::make_tuple(0, 0, 0),
           py::arg("frag_shift") = 32, py::arg("lo_shift") = 0, py::arg("narrow") = -1, py::arg("sample_stride") = 1,

@@ -973,7 +973,9 @@ struct BitmapSideArgs {
 
 // claimWords: an int64 window read through claim slices (the outer side of
 // bitmap_semi_rids: 16-byte loads of two words) instead of a segment table.
-BitmapSideArgs bitmapSide(const BitmapSide &s, const BitmapShape &sh, const char *name, bool claimWords = false) {
+// packedWords: the words are packed fragments; slices are whole 8-word chunks.
+BitmapSideArgs bitmapSide(const BitmapSide &s, const BitmapShape &sh, const char *name, bool claimWords = false,
+                          bool packedWords = false) {
   BitmapSideArgs out;
   const at::Tensor &w = s.window;
   TORCH_CHECK(w.is_cuda() && w.dim() == 1 && w.is_contiguous() &&
@@ -1017,8 +1019,10 @@ BitmapSideArgs bitmapSide(const BitmapSide &s, const BitmapShape &sh, const char
     at::Tensor ha = host(a), hc = host(c), he = host(e);
     const int64_t *pa = ha.data_ptr<int64_t>(), *pc = hc.data_ptr<int64_t>(), *pe = he.data_ptr<int64_t>();
     for (int64_t i = 0; i < ha.numel(); ++i) {
-      TORCH_CHECK(pa[i] >= 0 && pa[i] <= pe[i] && pa[i] <= pc[i] && pa[i] % 16 == 0, name, ": slice ", i,
-                  " must start on a 16-element boundary, not after its end or its cursor");
+      TORCH_CHECK(!packedWords || (pa[i] % 8 == 0 && pc[i] % 8 == 0 && pe[i] % 8 == 0), name, ": packed slice ", i,
+                  " must start, stand and end on 8-word chunk boundaries");
+      TORCH_CHECK(pa[i] >= 0 && pa[i] <= pe[i] && pa[i] <= pc[i] && (packedWords || pa[i] % 16 == 0), name, ": slice ",
+                  i, " must start on a 16-element boundary, not after its end or its cursor");
       if (pa[i] == pe[i]) continue;
       if (rm.on())
         TORCH_CHECK((pa[i] >> rm.lv) == ((pe[i] - 1) >> rm.lv) && ((uint64_t)pa[i] >> rm.lv) < (1ull << rm.lns),
@@ -1110,12 +1114,19 @@ py::dict opBitmapProbe(const BitmapSide &s, const at::Tensor &bitmaps, const Bit
   return bitmapCountersDict(ctr);
 }
 
-py::dict opBitmapJoin(const BitmapSide &r, const BitmapSide &s, const BitmapShape &sh) {
+// packed: int64 windows of packed fragment words (kernels.h, PK_*) read through
+// claim slices that count words.
+py::dict opBitmapJoin(const BitmapSide &r, const BitmapSide &s, const BitmapShape &sh, bool packed = false) {
   setDevice(r.window);
   TORCH_CHECK(r.window.device() == s.window.device() && r.window.scalar_type() == s.window.scalar_type(),
               "bitmap_join: inner and outer windows differ in device or element type");
   bitmapTotalWords(sh.bits);
-  BitmapSideArgs a = bitmapSide(r, sh, "bitmap_join inner"), b = bitmapSide(s, sh, "bitmap_join outer");
+  TORCH_CHECK(!packed || (r.window.scalar_type() == at::kLong && sh.keyShift == 0 &&
+                          sh.bits <= (int64_t)kernels::PK_FRAG_BITS),
+              "bitmap_join: packed windows are int64 words of fragments of at most ", kernels::PK_FRAG_BITS, " bits");
+  BitmapSideArgs a = bitmapSide(r, sh, "bitmap_join inner", packed, packed),
+                 b = bitmapSide(s, sh, "bitmap_join outer", packed, packed);
+  a.sl.packed = b.sl.packed = packed;
   at::Tensor ctr = at::zeros({4}, like(r.window));
   kernels::bitmapJoin(a.elemBytes, r.window.data_ptr(), s.window.data_ptr(), a.sl, b.sl, (uint32_t)sh.partitions,
                       (uint32_t)sh.keyShift, (uint32_t)sh.bits, ptr<kernels::BitmapCounters>(ctr), nullptr,
@@ -1708,6 +1719,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readwrite("bitmap_join", &core::JoinConfig::bitmapJoin)
       .def_readwrite("semi_bitmap", &core::JoinConfig::semiBitmap)
       .def_readwrite("replicate_bitmap", &core::JoinConfig::replicateBitmap)
+      .def_readwrite("packed_fragments", &core::JoinConfig::packedFragments)
       .def_readwrite("verify_exchange", &core::JoinConfig::verifyExchange)
       .def_readwrite("passes", &core::JoinConfig::passes)
       .def_readwrite("exchange", &core::JoinConfig::exchange)
@@ -1762,6 +1774,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def_readonly("bitmap_set", &core::JoinPlan::bitmapSet)
       .def_readonly("bitmap_bits", &core::JoinPlan::bitmapBits)
       .def_readonly("bitmap_replicated", &core::JoinPlan::bitmapReplicated)
+      .def_readonly("packed_fragments", &core::JoinPlan::packedFragments)
       .def_readonly("key_only", &core::JoinPlan::keyOnly)
       .def_readonly("inner_repeats", &core::JoinPlan::innerRepeats)
       .def_readonly("one_sided", &core::JoinPlan::oneSided)
@@ -2487,16 +2500,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       "bitmap_join",
       [](const at::Tensor &r, const at::Tensor &s, int64_t partitions, int64_t bits, OptT rStart, OptT rCur, OptT rEnd,
          OptT sStart, OptT sCur, OptT sEnd, OptT rSegStart, OptT rSegLen, OptT sSegStart, OptT sSegLen,
-         int64_t keyShift, int64_t threads, int64_t flat, OptT roundMeta) {
+         int64_t keyShift, int64_t threads, int64_t flat, OptT roundMeta, bool packed) {
         return opBitmapJoin(BitmapSide{r, rStart, rCur, rEnd, rSegStart, rSegLen},
                             BitmapSide{s, sStart, sCur, sEnd, sSegStart, sSegLen},
-                            BitmapShape{partitions, keyShift, bits, threads, flat, roundMeta});
+                            BitmapShape{partitions, keyShift, bits, threads, flat, roundMeta}, packed);
       },
       py::arg("r"), py::arg("s"), py::arg("partitions"), py::arg("bits"), py::arg("r_start") = py::none(),
       py::arg("r_cur") = py::none(), py::arg("r_end") = py::none(), py::arg("s_start") = py::none(),
       py::arg("s_cur") = py::none(), py::arg("s_end") = py::none(), py::arg("r_seg_start") = py::none(),
       py::arg("r_seg_len") = py::none(), py::arg("s_seg_start") = py::none(), py::arg("s_seg_len") = py::none(),
-      py::arg("key_shift") = 0, py::arg("threads") = 0, py::arg("flat") = -1, py::arg("round_meta") = py::none());
+      py::arg("key_shift") = 0, py::arg("threads") = 0, py::arg("flat") = -1, py::arg("round_meta") = py::none(),
+      py::arg("packed") = false);
   ops.def(
       "bitmap_semi_count",
       [](const at::Tensor &r, const at::Tensor &s, int64_t partitions, int64_t bits, OptT rStart, OptT rCur, OptT rEnd,

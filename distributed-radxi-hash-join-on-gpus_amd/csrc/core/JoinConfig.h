@@ -189,6 +189,15 @@ struct JoinConfig {
   // (2 (N-1)/N * 2^keyBits / 8) undercut the shuffle's; On: whenever the key
   // range fits (host path and N == 1 included); Off: never.
   PlanChoice replicateBitmap = PlanChoice::Auto;
+  // Packed fragment windows of the N = 1 counting bitmap plan (kernels.h, PK_*:
+  // three 20-bit fragments per 8-byte word, written in whole 64-byte chunks by
+  // a scatter that carries partial chunks in LDS): 2.67 instead of 4 bytes per
+  // fragment written and read back.  Auto: exactly when the plan is eligible --
+  // device engine, one rank, the counting bitmap plan (not the set plan, not
+  // materializing) in one pass (no partition groups), fragments of at most 20
+  // bits above at most 10 radix bits of keys of at most 32 bits.  On where the
+  // plan is not eligible is an error at construction; Off: u32 fragments.
+  PlanChoice packedFragments = PlanChoice::Auto;
   ExchangeMode exchange = ExchangeMode::Rccl;
   // N > 1: check the exchanged data, not only the counts -- content hashes
   // of every (source, chunk, partition) run on the sender vs what arrived
@@ -259,6 +268,7 @@ struct JoinPlan {
   uint32_t bitmapBits = 0;      // fragment bits per network partition (bitmap size 2^bitmapBits)
   bool bitmapSet = false;       // bitmapJoin with set semantics: semi / anti join (JoinConfig::semiBitmap)
   bool bitmapReplicated = false;  // bitmaps all-reduced over ranks, outer probed in place (tasks/BitmapJoin)
+  bool packedFragments = false;   // bitmapJoin over packed fragment windows (JoinConfig::packedFragments)
   bool oneSided = false;          // ExchangeMode::OneSided in effect (data::Window::enableOneSided)
   // Cost model of the N > 1 plan choice: bytes one rank puts on its links per
   // join for the replicated bitmaps and for the tuple shuffle, and the

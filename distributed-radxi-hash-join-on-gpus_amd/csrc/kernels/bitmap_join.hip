@@ -20,13 +20,17 @@
 //                counted (cross-rank duplicate check), the outer side probed
 // Elements are u32 key fragments of the count-only network pass (claim
 // slices of a sampled pass, read as 16-byte vectors: slices start on 16-
-// element boundaries) or 8-byte CompressedTuples (value >> keyShift) of an
-// exchanged window (host-built segment table).
+// element boundaries), 8-byte CompressedTuples (value >> keyShift) of an
+// exchanged window (host-built segment table), or -- bitmapJoin only -- packed
+// fragment words (kernels.h, PK_*: three 20-bit fragments and their count per
+// u64 word, claim slices counted in words and whole 64-byte chunks long; read
+// two words per 16-byte load, each word decoded on its own).
 #include "kernels.h"
 #include "device_common.h"
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 namespace hpcjoin {
 namespace kernels {
@@ -232,13 +236,146 @@ __device__ __forceinline__ void visitClaim(const uint32_t *__restrict__ src, con
   }
 }
 
+// Packed fragment words (kernels.h, PK_*): element type of a window whose u64
+// words hold up to three 20-bit fragments and their count in bits 60-63.
+struct PackedFrag {
+  uint64_t w;
+};
+using pk64x2 = unsigned long long __attribute__((ext_vector_type(2)));
+
+// fn(fragment) for the valid fragments of one packed word.
+template <typename Fn>
+__device__ __forceinline__ void visitPackedWord(uint64_t w, Fn &&fn) {
+  constexpr uint64_t M = (1ull << PK_FRAG_BITS) - 1;
+  const uint32_t c = (uint32_t)(w >> 60);
+  if (c > 0) fn(w & M);
+  if (c > 1) fn((w >> PK_FRAG_BITS) & M);
+  if (c > 2) fn((w >> (2 * PK_FRAG_BITS)) & M);
+}
+
+// visitSlice32 for packed words: src[b, b + len) in logical word positions, b
+// and len multiples of 8 (whole chunks: no remainder walk), 16-byte loads of
+// two words, batch k+1 in flight while batch k is consumed.
+template <int NTH, int U, typename Fn>
+__device__ __forceinline__ void visitSlicePacked(const uint64_t *__restrict__ src, uint64_t b, uint64_t len,
+                                                 const RoundMap &rm, Fn &&fn) {
+  const uint32_t t = threadIdx.x;
+  const uint64_t nv = len >> 1;
+  constexpr uint64_t STEP = (uint64_t)NTH * U;
+  pk64x2 cur[U], nxt[U];
+  auto load = [&](pk64x2(&x)[U], uint64_t i0) {
+#pragma unroll
+    for (int k = 0; k < U; ++k) {
+      const uint64_t i = i0 + (uint64_t)k * NTH + t;
+      if (i < nv) x[k] = __builtin_nontemporal_load(reinterpret_cast<const pk64x2 *>(src + rm(b + (i << 1))));
+    }
+  };
+  if (nv) load(cur, 0);
+  for (uint64_t i0 = 0; i0 < nv; i0 += STEP) {
+    if (i0 + STEP < nv) load(nxt, i0 + STEP);
+#pragma unroll
+    for (int k = 0; k < U; ++k) {
+      const uint64_t i = i0 + (uint64_t)k * NTH + t;
+      if (i < nv) {
+        visitPackedWord((uint64_t)cur[k].x, fn);
+        visitPackedWord((uint64_t)cur[k].y, fn);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < U; ++k) cur[k] = nxt[k];
+  }
+}
+
+// visitClaim for packed words: the partition's CLAIM_GROUPS slices as ONE
+// stream of 16-byte vectors of two words (slice starts and lengths are
+// multiples of 8 words).
+template <int NTH, int U, class Src, typename Fn>
+__device__ __forceinline__ void visitClaimPacked(const uint64_t *__restrict__ src, const Src &cs, uint32_t d,
+                                                 uint32_t &flags, Fn &&fn) {
+  constexpr uint32_t G = CLAIM_GROUPS;
+  __shared__ uint64_t sBase[G], sLen[G], sPre[G], sAdj[G];
+  const uint32_t t = threadIdx.x;
+  __syncthreads();  // an earlier walk's readers of the slice table are done
+  if (t < G) {
+    uint64_t b, len;
+    cs.get(d, t, b, len, flags);
+    sBase[t] = b;
+    sLen[t] = len;
+  }
+  __syncthreads();
+  if (t < G) {  // vector index i lies in slice g = max{g : pre[g] <= i}, at vector i + adj[g]
+    uint64_t pre = 0;
+    for (uint32_t j = 0; j < t; ++j) pre += sLen[j] >> 1;
+    sPre[t] = pre;
+    sAdj[t] = (sBase[t] >> 1) - pre;
+  }
+  __syncthreads();
+  const RoundMap rm = cs.roundMap();
+  static_assert(G == 8, "visitClaimPacked: the slice map is written out for 8 XCD groups");
+  const uint64_t p1 = uniform64(sPre[1]), p2 = uniform64(sPre[2]), p3 = uniform64(sPre[3]),
+                 p4 = uniform64(sPre[4]), p5 = uniform64(sPre[5]), p6 = uniform64(sPre[6]),
+                 p7 = uniform64(sPre[7]);
+  const uint64_t total = p7 + (uniform64(sLen[7]) >> 1);
+  const uint64_t a0 = uniform64(sAdj[0]), d1 = uniform64(sAdj[1] - sAdj[0]), d2 = uniform64(sAdj[2] - sAdj[1]),
+                 d3 = uniform64(sAdj[3] - sAdj[2]), d4 = uniform64(sAdj[4] - sAdj[3]),
+                 d5 = uniform64(sAdj[5] - sAdj[4]), d6 = uniform64(sAdj[6] - sAdj[5]),
+                 d7 = uniform64(sAdj[7] - sAdj[6]);
+  const pk64x2 *v = reinterpret_cast<const pk64x2 *>(src);
+  auto at = [&](uint64_t i) {
+    uint64_t a = a0;
+    a += i >= p1 ? d1 : 0;
+    a += i >= p2 ? d2 : 0;
+    a += i >= p3 ? d3 : 0;
+    a += i >= p4 ? d4 : 0;
+    a += i >= p5 ? d5 : 0;
+    a += i >= p6 ? d6 : 0;
+    a += i >= p7 ? d7 : 0;
+    return v + (rm((i + a) << 1) >> 1);
+  };
+  constexpr uint64_t STEP = (uint64_t)NTH * U;
+  pk64x2 cur[U], nxt[U];
+  auto load = [&](pk64x2(&x)[U], uint64_t i0) {
+#pragma unroll
+    for (int k = 0; k < U; ++k) {
+      const uint64_t i = i0 + (uint64_t)k * NTH + t;
+      if (i < total) x[k] = __builtin_nontemporal_load(at(i));
+    }
+  };
+  if (total) load(cur, 0);
+  for (uint64_t i0 = 0; i0 < total; i0 += STEP) {
+    if (i0 + STEP < total) load(nxt, i0 + STEP);
+#pragma unroll
+    for (int k = 0; k < U; ++k) {
+      const uint64_t i = i0 + (uint64_t)k * NTH + t;
+      if (i < total) {
+        visitPackedWord((uint64_t)cur[k].x, fn);
+        visitPackedWord((uint64_t)cur[k].y, fn);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < U; ++k) cur[k] = nxt[k];
+  }
+}
+
 // Every element of partition d of one side.  u32 fragments: one
 // flat walk over all claim slices (flat != 0: short partitions) or one
 // pipelined walk per slice (long partitions).
 template <int NTH, typename E, int U, class Src, typename Fn>
 __device__ __forceinline__ void visitPartition(const E *__restrict__ src, const Src &ss, uint32_t d, uint32_t shift,
                                                uint32_t flat, uint32_t &flags, Fn &&fn) {
-  if constexpr (sizeof(E) == 4) {
+  if constexpr (std::is_same_v<E, PackedFrag>) {  // the same two walks, chosen by the same rule
+    const uint64_t *words = reinterpret_cast<const uint64_t *>(src);
+    if (flat) {
+      visitClaimPacked<NTH, U>(words, ss, d, flags, fn);
+      return;
+    }
+    const RoundMap rm = ss.roundMap();
+    for (uint32_t g = 0; g < ss.groups(); ++g) {
+      uint64_t b, len;
+      ss.get(d, g, b, len, flags);
+      visitSlicePacked<NTH, U>(words, b, len, rm, fn);
+    }
+  } else if constexpr (sizeof(E) == 4) {
     if (flat) {
       visitClaim<NTH, U>(src, ss, d, flags, fn);
       return;
@@ -686,6 +823,27 @@ void bitmapJoin(uint32_t elemBytes, const void *r, const void *s, const BitmapSl
   const uint32_t words = bitmapWords(bits - split);
   const uint32_t flat = bmFlat(rsl, &ssl, partitions);
   const BitmapSlices &src = rsl;
+  HJ_CHECK(rsl.packed == ssl.packed, "bitmap join: inner and outer windows differ in format");
+  if (rsl.packed) {  // packed fragment words in claim slices of words
+    HJ_CHECK(elemBytes == 8 && keyShift == 0 && rsl.kind == BitmapSlices::Claim && bits <= PK_FRAG_BITS,
+             "bitmap join: packed fragments are 8-byte words in claim slices, at most %u bits", PK_FRAG_BITS);
+    const int nth = bmThreads(bits, src.threads);
+    using E = PackedFrag;
+    constexpr int U = BM_U;
+    auto go = [&](auto cur) {
+      using S = ClaimSrc<decltype(cur)>;
+      HJ_BM_NTH(hipLaunchKernelGGL((bitmapJoinKernel<E, U, S, NTH>), dim3(partitions), dim3(NTH), (size_t)words * 4,
+                                   st, static_cast<const E *>(r), static_cast<const E *>(s),
+                                   makeSrc<S>(rsl, partitions), makeSrc<S>(ssl, partitions), 0u, words, flat, 0u, out,
+                                   mb));
+    };
+    if (rsl.narrow)
+      go(uint32_t());
+    else
+      go((unsigned long long)0);
+    HIP_CHECK_LAUNCH();
+    return;
+  }
   HJ_BM_DISPATCH(hipLaunchKernelGGL((bitmapJoinKernel<E, U, S, NTH>), dim3(partitions << split), dim3(NTH),
                                     (size_t)words * 4, st,
                                     static_cast<const E *>(r), static_cast<const E *>(s), makeSrc<S>(rsl, partitions),
@@ -796,6 +954,8 @@ void preloadBitmapJoin() {
   hipFuncAttributes a;
   HIP_CHECK(hipFuncGetAttributes(
       &a, reinterpret_cast<const void *>(&bitmapJoinKernel<uint32_t, BM_U, ClaimSrc<uint32_t>, 1024>)));
+  HIP_CHECK(hipFuncGetAttributes(
+      &a, reinterpret_cast<const void *>(&bitmapJoinKernel<PackedFrag, BM_U, ClaimSrc<uint32_t>, 1024>)));
   HIP_CHECK(hipFuncGetAttributes(
       &a, reinterpret_cast<const void *>(&bitmapSemiCountKernel<BM_U, ClaimSrc<uint32_t>, 1024>)));
   HIP_CHECK(hipFuncGetAttributes(

@@ -194,6 +194,39 @@ void netScatterFrag(const data::Tuple *in, uint64_t n, uint32_t bits, const Part
                     uint32_t blockEnd, void *gcur, uint32_t *out, hipStream_t s, uint32_t keyBits,
                     KeyMix mix = KeyMix(), const void *gend = nullptr, int narrowMode = -1,
                     const uint32_t *roundMeta = nullptr);
+// Packed fragment window (JoinPlan::packedFragments: the N = 1 counting bitmap
+// plan whose fragments fit 20 bits).  An element of the window is one u64 word:
+//   bits  0-19, 20-39, 40-59   fragments 0, 1, 2
+//   bits 60-63                 valid fragments in the word (0-3), filled from
+//                              fragment 0 upwards
+// A chunk is 8 consecutive words (64 bytes, 64-byte aligned); a full chunk has
+// 3 valid fragments in every word, 24 in all.  The scatter writes nothing but
+// whole chunks: a workgroup carries every digit's partial tail in LDS across
+// its tiles (scatter_core.h), so only the last chunk a workgroup writes for a
+// digit may be partial (unused words have count 0).  Readers need no chunk
+// structure: they decode each word on its own.
+// Slice tables (gstart / gcur / gend), RoundMap positions and capacities count
+// words: every claim is 8 words from a slice start that is a multiple of 8, and
+// the round-interleaved layout keeps 4 KiB pieces (roundLpFor with 8-byte
+// elements).  2.67 bytes per fragment instead of 4.
+constexpr uint32_t PK_FRAG_BITS = 20;
+constexpr uint32_t PK_WORD_FRAGS = 3;
+constexpr uint32_t PK_CHUNK_WORDS = 8;
+constexpr uint32_t PK_CHUNK_FRAGS = PK_WORD_FRAGS * PK_CHUNK_WORDS;  // 24
+constexpr uint32_t PK_MAX_PART_BITS = 10;  // the scatter's LDS carry holds 24 fragments of 1024 digits
+HJ_HD uint64_t packFragments(uint32_t f0, uint32_t f1, uint32_t f2, uint32_t count) {
+  const uint64_t m = (1ull << PK_FRAG_BITS) - 1;
+  return (f0 & m) | ((f1 & m) << PK_FRAG_BITS) | ((f2 & m) << (2 * PK_FRAG_BITS)) | ((uint64_t)count << 60);
+}
+// The bounded claim scatter of all blocks of g into a packed window: gcur /
+// gend are [CLAIM_GROUPS][2^bits] word cursors laid out by netSampledLayout
+// with LayoutInput::packed (bits <= PK_MAX_PART_BITS; gend is required).  A
+// fragment (mixed key >> bits) wider than 20 bits is stored saturated and adds
+// 1 to *wideFlag (BitmapCounters::dup: the join falls back as for a fragment
+// outside the planned range).
+void netScatterFragPacked(const data::Tuple *in, uint64_t n, uint32_t bits, const PartitionGeometry &g, void *gcur,
+                          uint64_t *out, hipStream_t s, KeyMix mix, const void *gend, bool narrow,
+                          const uint32_t *roundMeta, unsigned long long *wideFlag);
 // Partition-group pass of the same scatter: only tuples whose digit is in
 // [dLo, dLo + range) are written, into [G][range] bounded claim slices (gcur /
 // gend laid out by netSampledLayout with the same range); the others are read
@@ -232,7 +265,18 @@ struct LayoutInput {
   uint32_t *roundMeta = nullptr;
   uint32_t roundLp = 0, roundMaxLv = 0;
   uint64_t roundCapacity = 0;
+  // Packed fragment window (PK_*): capacities in words -- a slice's fragment
+  // estimate / 3, rounded up to 16 words, plus packedTail words for the one
+  // partial chunk each workgroup of the claim group may leave
+  // (packedTailWords).  packed = false: one slot per tuple.
+  bool packed = false;
+  uint32_t packedTail = 0;
 };
+// Tail words per slice of a packed window: one chunk per workgroup that
+// claims from the slice (the blocks of one XCD group).
+inline uint32_t packedTailWords(const PartitionGeometry &g) {
+  return (g.blocks + CLAIM_GROUPS - 1) / CLAIM_GROUPS * PK_CHUNK_WORDS;
+}
 // Piece size (log2 slots) of a round-interleaved window of elemBytes-wide
 // words: JoinConfig::roundLp is given for 8-byte words; 4-byte fragment
 // windows use pieces of the same bytes.  0 = linear slices.
@@ -248,6 +292,9 @@ HJ_HD uint64_t roundSlots(uint64_t maxCap, uint32_t lp, uint32_t lns) {
 // estimate lands within 5 sigma of its group's mean (even data; skewed data
 // then gets linear slices inside the same window).
 uint64_t sampledWindowCapacity(const SampleScale &sc, uint32_t F, uint32_t roundLp);
+// The same for a packed fragment window, in words (LayoutInput::packed with
+// tailWords = packedTailWords(geometry); roundLp for 8-byte elements).
+uint64_t sampledPackedWindowCapacity(const SampleScale &sc, uint32_t F, uint32_t roundLp, uint32_t tailWords);
 // range > 0: lay out only digits [dLo, dLo + range) of the [G][F] totals, as
 // [G][range] slices (a partition-group pass, netScatterFragRange).
 void netSampledLayout(const LayoutInput *sides, uint32_t count, uint32_t F, bool narrow, hipStream_t s,
@@ -648,6 +695,8 @@ void groupEmitAgg(const BPArgs &a, const MarkUnit *units, const uint32_t *nUnits
 //                partitions given as the claim slices of a sampled pass
 //   elemBytes 8: CompressedTuples (fragment = value >> keyShift), partitions
 //                given as a segment table [F][groups] (exchanged windows)
+//   elemBytes 8 with BitmapSlices::packed (bitmapJoin only): packed fragment
+//                words (PK_*, three fragments each) in claim slices of words
 constexpr uint32_t BITMAP_MAX_BITS = 20;  // 128 KiB of LDS
 // The bitmap kernels may split a partition's fragment range over 2^split
 // workgroups (each holds one 128 KiB piece and reads all of the partition's
@@ -770,6 +819,9 @@ struct BitmapSlices {
   // Claim: device {lp, lv, lns, 0} of a round-interleaved fragment window
   // (RoundMap, LayoutInput::roundMeta); null = linear slices.
   const uint32_t *roundMeta = nullptr;
+  // Claim, bitmapJoin with elemBytes 8 only: the window holds packed fragment
+  // words (PK_*), the slices count words and are multiples of 8 long.
+  bool packed = false;
 };
 // u32 words of one partition's bitmap (a power of two >= 4).
 uint32_t bitmapWords(uint32_t bits);

@@ -513,6 +513,39 @@ void netScatterFrag(const data::Tuple *in, uint64_t n, uint32_t bits, const Part
   });
 }
 
+void netScatterFragPacked(const data::Tuple *in, uint64_t n, uint32_t bits, const PartitionGeometry &g, void *gcur,
+                          uint64_t *out, hipStream_t s, KeyMix mix, const void *gend, bool narrow,
+                          const uint32_t *roundMeta, unsigned long long *wideFlag) {
+  const bool any = netScatterArgs("netScatterFragPacked", n, bits, g, 0, g.blocks);
+  HJ_CHECK(bits <= PK_MAX_PART_BITS, "netScatterFragPacked: %u radix bits, the LDS carry holds 2^%u digits", bits,
+           PK_MAX_PART_BITS);
+  HJ_CHECK(gend && wideFlag, "netScatterFragPacked: bounded slices and a flag word are required");
+  if (!any) return;
+  const uint32_t F = 1u << bits;
+  const auto *src = reinterpret_cast<const ulonglong2 *>(in);
+  auto *dst = reinterpret_cast<unsigned long long *>(out);
+  auto go = [&](auto mixed, auto cur) {
+    using C = decltype(cur);
+    constexpr bool MIX = decltype(mixed)::value;
+    constexpr size_t lds = packedScatterLds<C>();
+    static_assert(lds <= 160 * 1024, "packed scatter: LDS carve exceeds a CU");
+    hipLaunchKernelGGL((netScatterFragPackedKernel<MIX, C>), dim3(g.blocks), dim3(CL_NTH), lds, s, src, n,
+                       g.tilesPerBlock, F, bits, mix, reinterpret_cast<C *>(gcur), dst,
+                       reinterpret_cast<const C *>(gend), roundMeta, wideFlag);
+  };
+  auto width = [&](auto mixed) {
+    if (narrow)
+      go(mixed, uint32_t());
+    else
+      go(mixed, (unsigned long long)0);
+  };
+  if (mix.on)
+    width(std::true_type());
+  else
+    width(std::false_type());
+  HIP_CHECK_LAUNCH();
+}
+
 void netScatterFragRange(const data::Tuple *in, uint64_t n, uint32_t bits, const PartitionGeometry &g, void *gcur,
                          uint32_t *out, hipStream_t s, uint32_t keyBits, KeyMix mix, const void *gend, bool narrow,
                          uint32_t dLo, uint32_t range) {
@@ -553,6 +586,7 @@ struct LayoutSideArgs {
   uint32_t *roundMeta;        // LayoutInput::roundMeta
   uint32_t roundLp, roundMaxLv;
   unsigned long long roundCapacity;
+  uint32_t packDiv, packTail;  // LayoutInput::packed: fragments per word (else 1), tail words per slice
 };
 
 // Workgroup i lays out side i (one or two sides per launch).
@@ -594,7 +628,9 @@ __global__ __launch_bounds__(LAY_NT) void netSampledLayoutKernel(LayoutSideArgs<
         c = fmin(ceil(est + margin), total);
       }
       if (ls.clear) ls.clear[(size_t)g * Fsrc + dLo + d] = 0;  // read once (above), by this thread
-      cap[k] = ((unsigned long long)c + 15ull) & ~15ull;
+      // Packed windows count words: ceil(fragments / 3), plus the workgroups' tail chunks.
+      const unsigned long long slots = ((unsigned long long)c + ls.packDiv - 1) / ls.packDiv;
+      cap[k] = ((slots + 15ull) & ~15ull) + ls.packTail;
       local += cap[k];
     }
   }
@@ -650,7 +686,8 @@ static LayoutSideArgs<CurT> layoutSide(const LayoutInput &x) {
                               static_cast<CurT *>(x.gstart), static_cast<CurT *>(x.gcur), static_cast<CurT *>(x.gend),
                               x.capacityUsed,
                               x.clearSampled ? const_cast<unsigned long long *>(sampled) : nullptr,
-                              x.roundMeta, x.roundLp, x.roundMaxLv, (unsigned long long)x.roundCapacity};
+                              x.roundMeta, x.roundLp, x.roundMaxLv, (unsigned long long)x.roundCapacity,
+                              x.packed ? PK_WORD_FRAGS : 1u, x.packed ? x.packedTail : 0u};
 }
 
 void netSampledLayout(const LayoutInput *sides, uint32_t count, uint32_t F, bool narrow, hipStream_t s, uint32_t dLo,
@@ -722,6 +759,25 @@ uint64_t sampledWindowCapacity(const SampleScale &sc, uint32_t F, uint32_t round
   return std::max<uint64_t>(bound, roundSlots((uint64_t)std::ceil(maxCap), roundLp, lns));
 }
 
+uint64_t sampledPackedWindowCapacity(const SampleScale &sc, uint32_t F, uint32_t roundLp, uint32_t tailWords) {
+  // Per slice: ceil(c / 3) rounded up to 16 words, plus the tail chunks.
+  const uint64_t perSlice = 17 + tailWords;
+  const uint64_t bound = sampledLayoutCapacityBound(sc, F) / PK_WORD_FRAGS + perSlice * NGROUPS * F + 4096;
+  if (!roundLp) return bound;
+  double maxCap = 0;  // the largest slice's fragments, as sampledWindowCapacity
+  for (uint32_t g = 0; g < NGROUPS; ++g) {
+    if (sc.total[g] <= 0) continue;
+    const double scale = sc.seen[g] > 0 ? sc.total[g] / sc.seen[g] : 1.0;
+    const double mean = sc.total[g] / F;
+    const double hi = mean + 5.0 * std::sqrt(std::max(mean, scale) * scale);
+    maxCap = std::max(maxCap, hi + sc.sigmas * std::sqrt(std::max(hi, scale) * scale) + sc.frac * hi + sc.floor + 16.0);
+  }
+  uint32_t lns = 0;
+  while ((1u << lns) < NGROUPS * F) ++lns;
+  const uint64_t maxWords = (uint64_t)std::ceil(maxCap) / PK_WORD_FRAGS + perSlice;
+  return std::max<uint64_t>(bound, roundSlots(maxWords, roundLp, lns));
+}
+
 uint64_t sampledLayoutCapacityBound(const SampleScale &sc, uint32_t F) {
   // Per group: sum_d est_d = total_g; sum_d sqrt(max(est_d,scale) * scale) <=
   // sqrt(F * scale * (total_g + F * scale)) (Cauchy-Schwarz); + ceil and the 16-tuple
@@ -740,6 +796,7 @@ uint64_t sampledLayoutCapacityBound(const SampleScale &sc, uint32_t F) {
 void preloadNetPartition() {
   hipFuncAttributes a;
   HIP_CHECK(hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&netHistogramKernel)));
+  HIP_CHECK(hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&netScatterFragPackedKernel<false, uint32_t>)));
 }
 
 }  // namespace kernels

@@ -671,5 +671,234 @@ static void withMaxd(uint32_t F, Fn &&fn) {
 constexpr int CL_NTH = 1024;
 constexpr int CL_IPT = 8;
 
+// ------------------------------------------------ packed fragment scatter
+// The count-only fragment scatter of the headline plan, writing the packed
+// window of kernels.h (PK_*): three 20-bit fragments per 8-byte word, and
+// nothing but whole, aligned 64-byte chunks of 24 fragments.  A digit's run in
+// one 8192-tuple tile (8 fragments at 1024 digits) is far short of a chunk, so
+// the workgroup carries every digit's partial tail (< 24 fragments) in LDS
+// from tile to tile and flushes (carry + run) / 24 chunks per tile; what is
+// left of the run becomes the new carry.  At the end of its range the
+// workgroup writes every non-empty carry as one last, partial chunk.
+//
+// Same tile pipeline as scatterTile (rank by LDS atomics, ldsBarrier, claims
+// issued before the scan, next tile prefetched into registers, trash stores
+// instead of divergent global stores, one claim atomic per (XCD group, digit)
+// and tile -- adding 0 when no chunk fills -- bounded slices), with 1024
+// threads = at most 1024 digits: thread t owns digit t (its carry length lives
+// in a register).
+//   rank | A | move the previous tile's tail into the carry, claim 8 k words |
+//   scan of (run length, k) in one packed word, chunk -> digit map | prefetch,
+//   staging | B | write-out: 8 lanes per chunk, lane j packs fragments 3j..3j+2
+//   of "carry, then the staged run" and stores one word.
+// The carry is updated one tile late (after the next tile's barrier A): the
+// write-out still reads the old carry, and this way no third barrier is needed.
+// LDS (1024 digits, 64-bit cursors): counters and per-digit records 24 KiB,
+// chunk map 2.6 KiB, staged tile 32 KiB, carry 96 KiB (fragment-major:
+// carry[s][digit], conflict-free for the owner threads) = 154.7 KiB.
+constexpr uint32_t PK_DIGITS = 1024;  // digits per workgroup (= CL_NTH)
+// Chunks one tile can flush: (23 carried per digit + the tile) / 24, padded.
+constexpr uint32_t PK_MAP = ((PK_CHUNK_FRAGS - 1) * PK_DIGITS + CL_NTH * CL_IPT) / PK_CHUNK_FRAGS + 22;
+static_assert(PK_MAP % 8 == 0, "packed scatter: the chunk map keeps the LDS carve 16-byte aligned");
+
+template <typename CurT>
+constexpr size_t packedScatterLds() {
+  return (size_t)PK_DIGITS * (8 + 2 * sizeof(CurT)) + PK_MAP * 2 + 64 + (size_t)CL_NTH * CL_IPT * 4 +
+         (size_t)PK_CHUNK_FRAGS * PK_DIGITS * 4;
+}
+
+template <bool MIX, typename CurT>
+__global__ __launch_bounds__(CL_NTH, ScatterOcc<CL_NTH>::value) void netScatterFragPackedKernel(
+    const ulonglong2 *__restrict__ in, uint64_t n, uint32_t tpb, uint32_t F, uint32_t bits, KeyMix mix,
+    CurT *__restrict__ gcur, unsigned long long *out, const CurT *__restrict__ gend,
+    const uint32_t *__restrict__ roundMeta, unsigned long long *__restrict__ wideFlag) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  using Pol = NetFragPolT<MIX>;  // the loads of the u32 fragment scatter (keys only, non-temporal)
+  constexpr uint32_t D = PK_DIGITS, NTH = CL_NTH, IPT = CL_IPT, TILE = NTH * IPT;
+  constexpr uint32_t FB = PK_FRAG_BITS, FMASK = (1u << FB) - 1, CF = PK_CHUNK_FRAGS, CW = PK_CHUNK_WORDS;
+  static_assert(D == NTH, "packed scatter: one thread per digit");
+  uint32_t *cnt = reinterpret_cast<uint32_t *>(smem);  // tile rank counters
+  uint32_t *info = cnt + D;                            // run start (14 bits) | first chunk << 14 | carry length << 25
+  CurT *wbq = reinterpret_cast<CurT *>(info + D);      // claimed position of the digit's chunk 0 minus 8 * first chunk
+  CurT *send = wbq + D;                                // slice ends
+  uint16_t *cmap = reinterpret_cast<uint16_t *>(send + D);  // digit of every chunk the tile flushes
+  uint32_t *wave = reinterpret_cast<uint32_t *>(cmap + PK_MAP);
+  uint32_t *val = wave + 16;                           // the staged tile: fragment | digit << 20
+  uint32_t *carry = val + TILE;                        // carry[s * D + digit], s < 24
+  const uint32_t t = threadIdx.x, lane = t & (WAVE - 1), wid = t / WAVE;
+  RoundMap om;  // output slot map, decided by the layout kernel (RoundMap)
+  if (roundMeta) {
+    om.lp = roundMeta[0];
+    om.lv = roundMeta[1];
+    om.lns = roundMeta[2];
+  }
+  const size_t grp = (size_t)(blockIdx.x % NGROUPS) * F;
+  gcur += grp;
+  cnt[t] = 0;
+  send[t] = t < F ? gend[grp + t] : (CurT)0;
+  __syncthreads();
+  const uint64_t begin = (uint64_t)blockIdx.x * tpb * PART_TILE;
+  const uint64_t end = min(n, begin + (uint64_t)tpb * PART_TILE);
+  const uint32_t mask = F - 1;
+  uint32_t c = 0;                            // fragments of digit t in the carry
+  // The pending carry update, carry[to + j] = val[from + j] for j < count, in
+  // one register: from | to << 16 | count << 24.
+  uint32_t mv = 0;
+  uint32_t tooWide = 0;
+  typename Pol::LoadT v[IPT];
+  ScatterProf pf;
+  auto moveTail = [&]() {
+    const uint32_t from = mv & 0xFFFFu, to = (mv >> 16) & 0xFFu, count = mv >> 24;
+#pragma unroll 1
+    for (uint32_t j = 0; j < count; ++j) carry[(to + j) * D + t] = val[from + j];
+  };
+  // Next tile into registers, as prefetchTile (indices past the range end read
+  // its last element), from a thread index the compiler cannot hoist out of
+  // the tile loop: the eight loop-invariant addresses it would otherwise keep
+  // (16 VGPRs) pushed the prefetched tile itself into scratch.
+  auto prefetch = [&](uint64_t nbase, uint32_t tt) {
+    const uint64_t last = end - 1;
+#pragma unroll
+    for (int i = 0; i < IPT; ++i) {
+      const uint64_t idx = nbase + (uint64_t)(i * NTH + tt);
+      v[i] = Pol::load(in + (idx < last ? idx : last));
+    }
+  };
+  auto tile = [&](auto fullTile, uint64_t base, uint32_t count) {
+    constexpr bool FULL = decltype(fullTile)::value;
+    pf.start();
+    uint32_t tt = t;
+    asm volatile("" : "+v"(tt));  // opaque per tile (see prefetch)
+    uint32_t r[IPT], sw[IPT];
+#pragma unroll
+    for (int i = 0; i < IPT; ++i) {
+      const uint32_t idx = i * NTH + t;
+      if (FULL || idx < count) {
+        const uint64_t k = mixKey<MIX>(mix, v[i]);
+        const uint32_t d = (uint32_t)k & mask;
+        const uint64_t f = k >> bits;
+        // A fragment above 20 bits is not truncated into one that could match:
+        // it is stored saturated and the join's fallback flag is raised.
+        const bool wide = (f >> FB) != 0;
+        tooWide |= wide ? 1u : 0u;
+        r[i] = atomicAdd(&cnt[d], 1u);
+        sw[i] = (wide ? FMASK : (uint32_t)f) | (d << FB);
+      }
+    }
+    pf.mark(0);
+    ldsBarrier();  // A: counts final; previous tile's write-out done
+    pf.mark(1);
+    moveTail();  // the previous tile's tail joins the carry (its staged run is still in val)
+    const uint32_t nn = cnt[t];
+    cnt[t] = 0;
+    const uint32_t tot = c + nn, k = tot / CF;
+    // One device atomic per digit claims the chunks this tile flushes (0 words
+    // when none fills; padding digits add 0 to the trash).
+    CurT *const claimAt = tt < F ? gcur + tt : reinterpret_cast<CurT *>(g_scatterTrash) + tt;
+    const CurT claim = atomicAdd(claimAt, (CurT)(k * CW));
+    pf.mark(2);
+    // One scan for both run starts (low half) and first chunks (high half).
+    const uint32_t packed = nn | (k << 16);
+    const uint32_t incl = waveInclusiveScan<uint32_t>(packed);
+    if (lane == WAVE - 1) wave[wid] = incl;
+    ldsBarrier();
+    uint32_t prefix = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < NTH / WAVE; ++w) {
+      const uint32_t x = wave[w];
+      if (w < (int)wid) prefix += x;
+      total += x;
+    }
+    const uint32_t excl = prefix + incl - packed;
+    const uint32_t n0 = excl & 0xFFFFu, k0 = excl >> 16;
+    info[t] = n0 | (k0 << 14) | (c << 25);
+#pragma unroll 1
+    for (uint32_t j = 0; j < k; ++j) cmap[k0 + j] = (uint16_t)t;
+    wbq[t] = claim - (CurT)(k0 * CW);
+    // The tail that stays: elements [max(24 k, c), tot) of "carry, then run".
+    const uint32_t lo = max(k * CF, c);
+    mv = (n0 + lo - c) | ((lo - k * CF) << 16) | ((tot - lo) << 24);
+    c = tot - k * CF;
+    ldsBarrier();  // run starts visible
+    // The next tile's loads overlap the staging and the write-out.  (Issued
+    // before the scan, as scatterTile's early prefetch does, they do not fit
+    // 128 VGPRs next to the scan: half of the loaded tile went to scratch.)
+    prefetch(base + TILE, tt);
+    pf.mark(3);
+    const uint32_t chunks = (uint32_t)__builtin_amdgcn_readfirstlane((int)(total >> 16));
+#pragma unroll
+    for (int i = 0; i < IPT; ++i) {
+      const uint32_t idx = i * NTH + t;
+      if (FULL || idx < count) r[i] += info[sw[i] >> FB] & 0x3FFFu;
+    }
+#pragma unroll
+    for (int i = 0; i < IPT; ++i) {
+      const uint32_t idx = i * NTH + t;
+      if (FULL || idx < count) val[r[i]] = sw[i];
+    }
+    pf.mark(4);
+    ldsBarrier();  // B: staged tile, chunk map and write bases visible
+    pf.mark(6);
+    // Write-out: chunk q of the tile by lanes 8 q' .. 8 q' + 7 (a wave stores
+    // eight whole chunks per instruction); lanes past the last chunk rebuild
+    // chunk 0 and store it to the trash.
+    const uint32_t w8 = t & (CW - 1);
+    for (uint32_t q0 = 0; q0 < chunks; q0 += NTH / CW) {
+      const uint32_t q = q0 + t / CW;
+      const bool have = q < chunks;
+      const uint32_t qq = have ? q : 0;
+      const uint32_t d = cmap[qq];
+      const uint32_t inf = info[d];
+      const uint32_t dn0 = inf & 0x3FFFu, dk0 = (inf >> 14) & 0x7FFu, dc = inf >> 25;
+      const uint32_t s0 = ((qq - dk0) * CW + w8) * PK_WORD_FRAGS;
+      unsigned long long word = (unsigned long long)PK_WORD_FRAGS << 60;
+#pragma unroll
+      for (uint32_t e = 0; e < PK_WORD_FRAGS; ++e) {
+        const uint32_t s = s0 + e;
+        // One LDS read: the carry sits TILE words behind the staged tile.
+        const uint32_t f = val[s < dc ? TILE + s * D + d : dn0 + (s - dc)];
+        word |= (unsigned long long)(f & FMASK) << (FB * e);
+      }
+      const CurT pos = wbq[d] + (CurT)(qq * CW + w8);
+      const bool ok = have && (pos | (CurT)(CW - 1)) < send[d];  // the whole chunk ends inside the slice
+      unsigned long long *p =
+          ok ? out + om((uint64_t)pos) : reinterpret_cast<unsigned long long *>(g_scatterTrash) + tt;
+      *p = word;
+    }
+    pf.mark(7);
+#ifdef HPCJOIN_SCATTER_PROF
+    ++pf.tiles;
+#endif
+  };
+  if (begin < end) prefetch(begin, t);
+  for (uint64_t base = begin; base < end; base += TILE) {
+    if (base + TILE <= end)
+      tile(std::true_type(), base, TILE);
+    else
+      tile(std::false_type(), base, (uint32_t)(end - base));
+  }
+  pf.flush();
+  __syncthreads();  // the last write-out has read the carry
+  moveTail();
+  // The tails: one last chunk per digit with a carry, counts per word.
+  if (c > 0) {  // only digits < F ever hold fragments
+    uint32_t te = t;
+    asm volatile("" : "+v"(te));  // recomputed here: kept from the kernel's start it cost a spill across the loop
+    const CurT pos = atomicAdd(gcur + te, (CurT)CW);
+    if (pos + (CurT)CW <= send[t]) {
+#pragma unroll
+      for (uint32_t w = 0; w < CW; ++w) {
+        const uint32_t have = c > PK_WORD_FRAGS * w ? min(c - PK_WORD_FRAGS * w, PK_WORD_FRAGS) : 0u;
+        unsigned long long word = (unsigned long long)have << 60;
+#pragma unroll
+        for (uint32_t e = 0; e < PK_WORD_FRAGS; ++e)
+          if (e < have) word |= (unsigned long long)(carry[(PK_WORD_FRAGS * w + e) * D + t] & FMASK) << (FB * e);
+        out[om((uint64_t)pos + w)] = word;
+      }
+    }
+  }
+  if (__ballot(tooWide != 0) != 0 && lane == 0) atomicAdd(wideFlag, 1ull);
+}
+
 }  // namespace kernels
 }  // namespace hpcjoin

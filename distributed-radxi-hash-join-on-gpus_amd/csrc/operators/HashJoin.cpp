@@ -449,6 +449,7 @@ void HashJoin::makeJoinPlan() {
     for (auto &e : ev)
       if (!e) HIP_CHECK(hipEventCreate(&e));
   planPasses();
+  planPackedFragments();
   if (ctx->onDevice() && config.reserveWorkspace && passes == 1) {
     // Capped by what HBM has free (the estimate is generous for N > 1, where
     // received sizes are only known after the histogram): a short estimate
@@ -544,6 +545,18 @@ std::vector<uint64_t> HashJoin::workspaceParts() const {
       parts.push_back((sampledCap(n[0], lp) + 64) * 4);
       parts.push_back((sampledCap(n[1], kernels::roundLpFor(plan.roundLp, 8)) + 64) * 8);
       parts.push_back((n[1] + 2) * 8);
+      return parts;
+    }
+    if (plan.packedFragments) {  // packed windows: words, tail chunks included (tasks/BitmapJoin::sidePlan)
+      for (int r = 0; r < 2; ++r) {
+        const kernels::PartitionGeometry geom = kernels::partitionGeometry(n[r], config.maxPartitionBlocks);
+        const uint32_t stride = kernels::sampleStrideFor(geom, n[r], F, std::max<uint32_t>(1, config.sampleStride));
+        parts.push_back((kernels::sampledPackedWindowCapacity(kernels::sampleScale(geom, n[r], stride, false), F,
+                                                              kernels::roundLpFor(plan.roundLp, 8),
+                                                              kernels::packedTailWords(geom)) +
+                         64) *
+                        8);
+      }
       return parts;
     }
     for (int r = 0; r < 2; ++r) parts.push_back((sampledCap(n[r], lp) + 64) * 4);
@@ -711,6 +724,22 @@ void HashJoin::planBitmap() {
   plan.bitmapSet = set;
   plan.bitmapReplicated = N > 1;
   plan.sampledNetwork = !bitmapExact;
+}
+
+// Packed fragment windows (JoinConfig::packedFragments; kernels.h, PK_*), once
+// the bitmap plan and its passes are known: the headline plan only.  Every
+// other plan keeps u32 fragments: the set plan, partition-group passes, N > 1,
+// keys above 32 bits (digit-array scatter policy), the host path -- and the
+// two-level plan a bitmap join falls back to (basePlan never has it).
+void HashJoin::planPackedFragments() {
+  const bool eligible = ctx->onDevice() && numberOfNodes == 1 && passes == 1 && plan.bitmapJoin && !plan.bitmapSet &&
+                        !plan.materialize && plan.groupBudget == 0 && plan.bitmapBits <= kernels::PK_FRAG_BITS &&
+                        plan.networkBits <= kernels::PK_MAX_PART_BITS && plan.keyBits <= 32;
+  JOIN_ASSERT(eligible || config.packedFragments != core::PlanChoice::On, "HashJoin",
+              "JoinConfig.packedFragments (packed_fragments) = On, but the plan is not the single-pass counting bitmap "
+              "plan of one device rank with fragments of at most %u bits: %s",
+              kernels::PK_FRAG_BITS, plan.describe().c_str());
+  plan.packedFragments = eligible && config.packedFragments != core::PlanChoice::Off;
 }
 
 // Wire codec per relation (kernels.h, WireCodec): frame-of-reference rids

@@ -176,6 +176,7 @@ class HashJoin {
   void planPasses();
   JoinResult runPasses();
   void planBitmap();
+  void planPackedFragments();
   void recordTimes(const JoinRun &run, uint64_t t4);
   bool lowKeyBitsSkewed();
  public:

@@ -51,16 +51,18 @@ const BitmapJoin::SidePlan &BitmapJoin::sidePlan(uint64_t n, bool exact, uint32_
   struct Key {
     uint64_t n;
     uint32_t maxBlocks, bits, stride, lp;
-    bool exact;
+    bool exact, packed;
     bool operator<(const Key &o) const {
-      return std::tie(n, maxBlocks, bits, stride, lp, exact) <
-             std::tie(o.n, o.maxBlocks, o.bits, o.stride, o.lp, o.exact);
+      return std::tie(n, maxBlocks, bits, stride, lp, exact, packed) <
+             std::tie(o.n, o.maxBlocks, o.bits, o.stride, o.lp, o.exact, o.packed);
     }
   };
   thread_local std::map<Key, SidePlan> cache;
   const uint32_t F = 1u << plan.networkBits;
   const uint32_t lp = kernels::roundLpFor(plan.roundLp, elemBytes);
-  const Key k{n, maxBlocks, plan.networkBits, stride, lp, exact};
+  // Packed fragment windows (both sides, 8-byte words): the capacity counts words.
+  const bool packed = plan.packedFragments && elemBytes == 8;
+  const Key k{n, maxBlocks, plan.networkBits, stride, lp, exact, packed};
   auto it = cache.find(k);
   if (it != cache.end()) return it->second;
   if (cache.size() > 64) cache.clear();
@@ -68,7 +70,8 @@ const BitmapJoin::SidePlan &BitmapJoin::sidePlan(uint64_t n, bool exact, uint32_
   sp.geom = kernels::partitionGeometry(n, maxBlocks);
   sp.stride = exact ? 1 : kernels::sampleStrideFor(sp.geom, n, F, stride);
   sp.sc = kernels::sampleScale(sp.geom, n, sp.stride, exact);
-  sp.cap = kernels::sampledWindowCapacity(sp.sc, F, lp);
+  sp.cap = packed ? kernels::sampledPackedWindowCapacity(sp.sc, F, lp, kernels::packedTailWords(sp.geom))
+                  : kernels::sampledWindowCapacity(sp.sc, F, lp);
   return cache.emplace(k, sp).first->second;
 }
 
@@ -110,6 +113,8 @@ void BitmapJoin::layoutSides(Side *sides, uint32_t count, bool exact, bool narro
     lay[i].sampled = in[i].totals;
     lay[i].sc = sc;
     lay[i].clearSampled = useControl;
+    lay[i].packed = s.packed;
+    lay[i].packedTail = s.packed ? kernels::packedTailWords(s.geom) : 0;
   }
   if (sampled) {
     kernels::netSampledTotals(in, count, bits, st, mix, useControl);
@@ -157,6 +162,7 @@ void BitmapJoin::layoutSides(Side *sides, uint32_t count, bool exact, bool narro
     s.slices.threads = plan.variants.bmThreads;
     s.slices.flat = plan.variants.bmFlat;
     s.slices.roundMeta = lay[i].roundMeta;
+    s.slices.packed = s.packed;
     s.frags = static_cast<uint32_t *>(ws.get(std::max<uint64_t>(s.cap, 16) * s.elemBytes));
   }
   kernels::netSampledLayout(lay, count, F, narrow, st);
@@ -165,6 +171,13 @@ void BitmapJoin::layoutSides(Side *sides, uint32_t count, bool exact, bool narro
 // The bounded claim scatter of one side's u32 fragments into its slices.
 void BitmapJoin::scatterSide(Side &s) {
   const kernels::KeyMix mix{plan.keyMix ? 1u : 0u, plan.keyBits};
+  if (s.packed) {  // packed fragment words in whole chunks; a fragment above 20 bits raises the dup flag
+    kernels::netScatterFragPacked(s.relation->getData(), s.relation->getLocalSize(), plan.networkBits, s.geom,
+                                  const_cast<void *>(s.slices.cur), reinterpret_cast<uint64_t *>(s.frags),
+                                  ctx->stream(), mix, s.slices.end, s.slices.narrow, s.slices.roundMeta,
+                                  &counters->dup);
+    return;
+  }
   if (s.elemBytes == 8) {  // CompressedTuples (fragment << keyShift | rid) into the same bounded claim slices
     kernels::netScatter(s.relation->getData(), s.relation->getLocalSize(), plan.networkBits, plan.keyShift, s.geom, 0,
                         s.geom.blocks, const_cast<void *>(s.slices.cur), reinterpret_cast<uint64_t *>(s.frags),
@@ -372,18 +385,26 @@ BitmapJoin::Outcome BitmapJoin::runDevice(bool exact) {
     cnt = ws.getArray<BitmapCounters>(1);
     ctx->zero(cnt, sizeof(BitmapCounters));
   }
+  counters = cnt;
   Outcome o;
   // One cursor width for both sides (the fused N = 1 kernel reads both with
   // one slice type; e.g. 1B inner x 4B outer needs 8-byte cursors on both).
   const bool setRids = plan.bitmapSet && plan.materialize;
-  const uint32_t outerBytes = setRids ? 8 : 4;
-  const bool narrowOk = sideNarrow(inner, exact) && sideNarrow(outer, exact, outerBytes);
+  // Packed fragment windows (HashJoin::planPackedFragments: N = 1, counting):
+  // both sides are 8-byte words of three fragments.
+  const bool packed = plan.packedFragments;
+  JOIN_ASSERT(!packed || (N == 1 && !plan.bitmapSet && !plan.materialize && bits <= kernels::PK_FRAG_BITS),
+              "BitmapJoin", "packed fragments need the counting plan of one rank (fragment bits %u)", bits);
+  const uint32_t innerBytes = packed ? 8 : 4, outerBytes = setRids || packed ? 8 : 4;
+  const bool narrowOk = sideNarrow(inner, exact, innerBytes) && sideNarrow(outer, exact, outerBytes);
   // Time points (one event each, shared by the spans that meet there):
   // ev[0] join start, ev[1] inner side partitioned, ev[2] outer side
   // partitioned, ev[3] probe start (N > 1: after the all-reduce), ev[4] end.
   performance::Timeline &tl = ctx->timeline();
   Side both[2] = {Side{inner, {}, nullptr, {}}, Side{outer, {}, nullptr, {}}};
+  both[0].elemBytes = innerBytes;
   both[1].elemBytes = outerBytes;
+  both[0].packed = both[1].packed = packed;
   unsigned long long *ridOut = nullptr, *ridCursor = nullptr;
   const uint64_t ridCapacity = outer->getLocalSize();
   if (setRids) {  // one rid per outer tuple at most: the output cannot overflow
@@ -431,7 +452,7 @@ BitmapJoin::Outcome BitmapJoin::runDevice(bool exact) {
     else if (plan.bitmapSet)
       kernels::bitmapSemiCount(ri.frags, ro.frags, ri.slices, ro.slices, F, bits, cnt, st, mb);
     else
-      kernels::bitmapJoin(4, ri.frags, ro.frags, ri.slices, ro.slices, F, 0, bits, cnt, st, mb);
+      kernels::bitmapJoin(packed ? 8 : 4, ri.frags, ro.frags, ri.slices, ro.slices, F, 0, bits, cnt, st, mb);
     HIP_CHECK(hipEventRecord(ev[4], st));
     tl.endAt("BPKERNEL", ev[4]);
     tl.endAt("BPTASKTIME", ev[4]);

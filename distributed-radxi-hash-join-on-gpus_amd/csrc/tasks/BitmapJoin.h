@@ -96,6 +96,9 @@ class BitmapJoin {
     kernels::BitmapSlices slices;
     uint64_t cap = 0;  // fragment capacity of all slices
     uint32_t elemBytes = 4;  // 8: CompressedTuples with rids (the outer side of a materializing set join)
+    // Packed fragment window (JoinPlan::packedFragments; elemBytes 8): frags
+    // holds u64 words of three fragments, cap and the slices count words.
+    bool packed = false;
   };
   // narrowOk: 4-byte claim cursors are allowed (both sides of a fused bitmap
   // join must use the same cursor width; sideNarrow() says what one side needs).
@@ -125,6 +128,7 @@ class BitmapJoin {
   hipEvent_t *ev;
   bool useControl = false;   // N = 1 device engine: control-block scratch + mailbox result
   uint64_t mailboxSeq = 0;
+  kernels::BitmapCounters *counters = nullptr;  // the running join's device counters (runDevice)
 };
 
 }  // namespace tasks

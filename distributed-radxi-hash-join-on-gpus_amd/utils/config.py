@@ -26,6 +26,7 @@ def config_to_dict(cfg) -> dict:
     d["local_histogram"] = str(cfg.local_histogram).split(".")[-1]
     d["wire_codec"] = str(cfg.wire_codec).split(".")[-1]
     d["replicate_bitmap"] = str(cfg.replicate_bitmap).split(".")[-1]
+    d["packed_fragments"] = str(cfg.packed_fragments).split(".")[-1]
     d["exchange"] = str(cfg.exchange).split(".")[-1]
     d["kind"] = str(cfg.kind).split(".")[-1]
     return d
@@ -41,7 +42,7 @@ def config_from_dict(d: dict | None = None, env_prefix: str = "HPCJOIN_"):
     cfg = C.JoinConfig()
     merged = dict(d or {})
     for f in _FIELDS + ["assignment", "format", "key_hashing", "network_histogram", "local_histogram", "wire_codec",
-                        "replicate_bitmap", "exchange", "verify_exchange", "kind"]:
+                        "replicate_bitmap", "packed_fragments", "exchange", "verify_exchange", "kind"]:
         v = os.environ.get(env_prefix + f.upper())
         if v is not None:
             merged[f] = v
@@ -58,7 +59,7 @@ def config_from_dict(d: dict | None = None, env_prefix: str = "HPCJOIN_"):
             setattr(cfg, k, v if isinstance(v, bool) else str(v).lower() in ("1", "true", "yes"))
         elif k == "wire_codec":
             cfg.wire_codec = getattr(C.WireCodecMode, str(v).upper())
-        elif k in ("replicate_bitmap", "verify_exchange"):
+        elif k in ("replicate_bitmap", "packed_fragments", "verify_exchange"):
             setattr(cfg, k, getattr(C.PlanChoice, str(v).upper()))
         elif k == "kind":
             cfg.kind = getattr(C.JoinKind, str(v).upper())

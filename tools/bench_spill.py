@@ -57,6 +57,9 @@ def main():
     probe = C.JoinConfig()
     probe.reserve_workspace = False
     probe.passes = 1
+    # The estimate of the plan that spills: partition-group passes keep u32 fragments, so the budget is a
+    # fraction of the u32 windows (the packed windows of the unconstrained plan are a third smaller).
+    probe.packed_fragments = C.PlanChoice.OFF
     est = C.HashJoin(R, S, ctx, probe).workspace_estimate()
     cfg = C.JoinConfig()
     cfg.passes = args.passes
