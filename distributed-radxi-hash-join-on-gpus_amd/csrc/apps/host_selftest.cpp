@@ -9,6 +9,7 @@
 //   host_selftest [--ranks N] [--size G]
 // Exit code 0 iff every join matches its oracle.
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -47,13 +48,25 @@ struct Case {
   bool groupValues = false;
   // kind Group: sum, min and max of three strided outer columns per group (HashJoin::joinGroupAgg; one rank)
   bool groupAgg = false;
+  // kind Group: typed columns -- float64 sum, float32 min (stride 2), int32 max (stride 3) per group
+  bool groupTyped = false;
 };
 
 // The value of outer tuple `rid` in the group-join cases: spread over the int64 range, so the sums wrap.
 uint64_t groupValue(uint64_t rid) { return kernels::mix64(rid + 77) * 0x9E3779B97F4A7C15ull; }
+// The typed columns of outer tuple `rid`: multiples of 1/8 below 2^27 (every partial sum is exact in binary64,
+// whatever the order), float32 values exact in their type, and int32 values over the whole range.
+double groupF64(uint64_t rid) { return (double)((int64_t)(groupValue(rid) >> 33) - (int64_t(1) << 30)) / 8.0; }
+float groupF32(uint64_t rid) { return (float)((int64_t)(groupValue(rid + 5) >> 43) - (int64_t(1) << 20)) / 8.0f; }
+int32_t groupI32(uint64_t rid) { return (int32_t)(uint32_t)(groupValue(rid + 9) >> 32); }
+uint64_t bitsOf(double d) {
+  uint64_t b;
+  std::memcpy(&b, &d, 8);
+  return b;
+}
 
 bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
-  if (c.semiBitmap || c.groupValues || c.groupAgg) ranks = 1;
+  if (c.semiBitmap || c.groupValues || c.groupAgg || c.groupTyped) ranks = 1;
   auto group = std::make_shared<comm::InProcessGroup>(ranks);
   std::vector<std::string> errors(ranks);
   std::vector<uint64_t> matches(ranks, 0), pairs(ranks, 0);
@@ -91,7 +104,7 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
       cfg.chunks = 2;
       cfg.wireCodec = c.wire ? core::WireCodecMode::On : core::WireCodecMode::Off;
       cfg.semiBitmap = c.semiBitmap;
-      if (c.groupAgg) cfg.groupColumns = 3;
+      if (c.groupAgg || c.groupTyped) cfg.groupColumns = 3;
       operators::HashJoin j(&R, &S, &ctx, cfg);
       if (c.semiBitmap && !(j.getPlan().bitmapJoin && j.getPlan().bitmapSet))
         throw std::runtime_error("the set bitmap plan was not taken");
@@ -113,11 +126,36 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
         cols.agg[1] = kernels::GROUP_MIN;
         cols.agg[2] = kernels::GROUP_MAX;
       }
-      operators::JoinResult res = c.groupAgg      ? j.joinGroupAgg(cols, 0, GS)
+      std::vector<double> f64;
+      std::vector<float> f32;
+      std::vector<int32_t> i32;
+      if (c.groupTyped) {  // one tensor per type; the 4-byte columns are strided views (element strides 2 and 3)
+        f64.resize(GS);
+        f32.assign(2 * GS, 0.0f);
+        i32.assign(3 * GS, 0);
+        for (uint64_t i = 0; i < GS; ++i) {
+          f64[i] = groupF64(i);
+          f32[2 * i + 1] = groupF32(i);
+          i32[3 * i + 2] = groupI32(i);
+        }
+        cols.n = 3;
+        cols.col[0] = f64.data();
+        cols.col[1] = f32.data() + 1;
+        cols.col[2] = i32.data() + 2;
+        cols.stride[1] = 2;
+        cols.stride[2] = 3;
+        cols.dtype[0] = kernels::GROUP_F64;
+        cols.dtype[1] = kernels::GROUP_F32;
+        cols.dtype[2] = kernels::GROUP_I32;
+        cols.agg[0] = kernels::GROUP_SUM;
+        cols.agg[1] = kernels::GROUP_MIN;
+        cols.agg[2] = kernels::GROUP_MAX;
+      }
+      operators::JoinResult res = c.groupAgg || c.groupTyped ? j.joinGroupAgg(cols, 0, GS)
                                   : c.groupValues ? j.joinGroup(values.data() + 1, 0, GS, 3)
                                                   : j.run();
       if (groupKind) {
-        const uint64_t W = c.groupAgg ? 5 : c.groupValues ? 3 : 2;
+        const uint64_t W = c.groupAgg || c.groupTyped ? 5 : c.groupValues ? 3 : 2;
         if (res.localMatches != res.outputGroups || res.unmatchedOuter != 0 || res.outputPairs != 0 ||
             res.outputRids != 0 || res.groupSums != c.groupValues || res.groupColumns != W - 2 || !j.getOutputGroups())
           throw std::runtime_error("group join: the result fields do not add up");
@@ -235,6 +273,11 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
       int64_t min = INT64_MAX, max = INT64_MIN;
     };
     std::unordered_map<uint64_t, Agg> aggByKey;  // groupAgg: outer key -> (sum of word 0, min of word 1, max of word 2)
+    struct Typed {
+      double sum = 0.0, min = HUGE_VAL;
+      int64_t max = INT64_MIN;
+    };
+    std::unordered_map<uint64_t, Typed> typedByKey;  // groupTyped: outer key -> (float64 sum, float32 min, int32 max)
     for (uint64_t i = 0; i < GS; ++i) {
       auto &e = byKey[S.getData()[i].key];
       ++e.first;
@@ -246,10 +289,17 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
         g.min = std::min(g.min, (int64_t)groupValue(3 * rid + 1));
         g.max = std::max(g.max, (int64_t)groupValue(3 * rid + 2));
       }
+      if (c.groupTyped) {
+        Typed &g = typedByKey[S.getData()[i].key];
+        const uint64_t rid = S.getData()[i].rid;
+        g.sum += groupF64(rid);
+        g.min = std::min(g.min, (double)groupF32(rid));
+        g.max = std::max(g.max, (int64_t)groupI32(rid));
+      }
     }
     std::unordered_map<uint64_t, uint64_t> keyOf;  // inner rid -> key
     for (uint64_t i = 0; i < G; ++i) keyOf[R.getData()[i].rid] = R.getData()[i].key;
-    const uint64_t W = c.groupAgg ? 5 : c.groupValues ? 3 : 2;
+    const uint64_t W = c.groupAgg || c.groupTyped ? 5 : c.groupValues ? 3 : 2;
     std::unordered_set<uint64_t> seen;
     uint64_t repeated = 0, empty = 0;
     for (const auto &v : groups)
@@ -265,6 +315,10 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
         if (c.groupAgg) {  // an empty group carries the identities
           const Agg g = e == byKey.end() ? Agg() : aggByKey[k->second];
           if (v[i + 2] != g.sum || (int64_t)v[i + 3] != g.min || (int64_t)v[i + 4] != g.max) ok = false;
+        }
+        if (c.groupTyped) {  // bit for bit: +0.0 and +inf in the float words of an empty group, INT64_MIN in the int32's
+          const Typed g = e == byKey.end() ? Typed() : typedByKey[k->second];
+          if (v[i + 2] != bitsOf(g.sum) || v[i + 3] != bitsOf(g.min) || (int64_t)v[i + 4] != g.max) ok = false;
         }
         empty += cnt == 0;
       }
@@ -362,6 +416,8 @@ int main(int argc, char **argv) {
        core::JoinKind::Group, false, true},
       {"group_zipf_sum_min_max", kernels::KeyDistribution::Zipf, false, true, false, core::KeyHashing::Auto, false,
        core::JoinKind::Group, false, false, true},
+      {"group_zipf_typed_f64_f32_i32", kernels::KeyDistribution::Zipf, false, true, false, core::KeyHashing::Auto, false,
+       core::JoinKind::Group, false, false, false, true},
       {"semi_bitmap_zipf_rids", kernels::KeyDistribution::Zipf, false, true, false, core::KeyHashing::Auto, false,
        core::JoinKind::Semi, true},
       {"semi_bitmap_uniform_count", kernels::KeyDistribution::Uniform, false, false, false, core::KeyHashing::Auto,

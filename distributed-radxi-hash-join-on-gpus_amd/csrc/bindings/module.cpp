@@ -680,6 +680,13 @@ py::dict opBuildProbeOuterRows(const at::Tensor &R, const at::Tensor &S, const a
   return buildProbeOuterImpl(R, S, partR, partS, fragShift, keyShift, wide, rChunk, sChunk, keepInner, keepOuter, &pr);
 }
 
+static bool groupDtypeOf(at::ScalarType t, uint32_t &code);
+static std::string groupTorchDtypeName(at::ScalarType t);
+py::dict opBuildProbeGroupAgg(const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR, const at::Tensor &partS,
+                              int64_t fragShift, int64_t keyShift, bool wide, int64_t rChunk, int64_t sChunk,
+                              const std::vector<at::Tensor> &columns, const std::vector<std::string> &aggs,
+                              int64_t ridOffset);
+
 // ---- group join over partition-major inputs: LDS counters / sums, inner units, rows ----
 // rows: int64 [|R|, 2] (inner rid, count) or, with values, [|R|, 3] (inner rid,
 // count, sum); counts / sums: the raw accumulators by position of R (int64;
@@ -694,6 +701,17 @@ py::dict opBuildProbeGroup(const at::Tensor &R, const at::Tensor &S, const at::T
   const bool sum = values.has_value() && values->defined();
   const unsigned long long *vals = nullptr;
   uint64_t stride = 1;
+  if (sum && values->dim() == 1 && values->scalar_type() != at::kLong) {
+    // int32, float64 or float32 values: the aggregate path with one "sum" column ("sums": the int64 words of its
+    // accumulators, binary64 bits for the float types); every other dtype is refused here.
+    uint32_t code = 0;
+    TORCH_CHECK(groupDtypeOf(values->scalar_type(), code), "build_probe_group: values have dtype ",
+                groupTorchDtypeName(values->scalar_type()), "; a 1-D int64, int32, float64 or float32 tensor is needed");
+    py::dict d = opBuildProbeGroupAgg(R, S, partR, partS, fragShift, keyShift, wide, rChunk, sChunk, {*values}, {"sum"},
+                                      ridOffset);
+    d["sums"] = d["aggs"].cast<at::Tensor>().select(0, 0);
+    return d;
+  }
   if (sum) {
     const at::Tensor &v = *values;
     TORCH_CHECK(v.dim() == 1 && v.scalar_type() == at::kLong && v.device() == R.device(),
@@ -790,8 +808,43 @@ py::dict opBuildProbeGroup(const at::Tensor &R, const at::Tensor &S, const at::T
   return d;
 }
 
+// The element types a group join aggregates (kernels::GroupDtype); false for any other torch dtype.
+static bool groupDtypeOf(at::ScalarType t, uint32_t &code) {
+  switch (t) {
+    case at::kLong: code = kernels::GROUP_I64; return true;
+    case at::kInt: code = kernels::GROUP_I32; return true;
+    case at::kDouble: code = kernels::GROUP_F64; return true;
+    case at::kFloat: code = kernels::GROUP_F32; return true;
+    default: return false;
+  }
+}
+// torch's own spelling ("float16", "bool", "uint8", ...), as the caller wrote it.
+static std::string groupTorchDtypeName(at::ScalarType t) {
+  std::string s = c10::toString(t);  // "Half", "Bool", "Byte", ...
+  switch (t) {
+    case at::kHalf: return "float16";
+    case at::kBFloat16: return "bfloat16";
+    case at::kByte: return "uint8";
+    case at::kChar: return "int8";
+    case at::kShort: return "int16";
+    case at::kInt: return "int32";
+    case at::kLong: return "int64";
+    case at::kFloat: return "float32";
+    case at::kDouble: return "float64";
+    case at::kBool: return "bool";
+    default: return s;
+  }
+}
+// Row-word dtypes of a result, one per column: "int64", or "float64" for the bits of a binary64.
+static py::list groupWordDtypes(const kernels::GroupColumns &c) {
+  py::list l;
+  for (uint32_t i = 0; i < c.n; ++i) l.append(kernels::groupDtypeIsFloat(c.dtype[i]) ? "float64" : "int64");
+  return l;
+}
+
 // columns / aggs of join_group_agg and build_probe_group_agg -> kernels::GroupColumns (offset and rows left to the
-// caller): 1-D int64 tensors of `rows` entries where `device` says, "sum" | "min" | "max" in any letter case.
+// caller): 1-D int64, int32, float64 or float32 tensors of `rows` entries where `device` says (strides in elements
+// of the column's own dtype), "sum" | "min" | "max" in any letter case.
 static kernels::GroupColumns groupColumnsOf(const char *who, const std::vector<at::Tensor> &columns,
                                             const std::vector<std::string> &aggs, bool onDevice, int64_t rows) {
   TORCH_CHECK(!columns.empty() && columns.size() <= kernels::GROUP_MAX_COLUMNS, who, ": ", columns.size(),
@@ -807,12 +860,14 @@ static kernels::GroupColumns groupColumnsOf(const char *who, const std::vector<a
     TORCH_CHECK(name == "sum" || name == "min" || name == "max", who, ": unknown aggregate '", aggs[i],
                 "' of column ", i, " (sum, min or max; AVG is sum / count on the caller's side)");
     c.agg[i] = name == "sum" ? kernels::GROUP_SUM : name == "min" ? kernels::GROUP_MIN : kernels::GROUP_MAX;
-    TORCH_CHECK(v.dim() == 1 && v.scalar_type() == at::kLong, who, ": column ", i, " must be a 1-D int64 tensor");
+    TORCH_CHECK(v.dim() == 1 && groupDtypeOf(v.scalar_type(), c.dtype[i]), who, ": column ", i,
+                " must be a 1-D int64 tensor (or int32, float64, float32); it has ", v.dim(), " dimension(s) and dtype ",
+                groupTorchDtypeName(v.scalar_type()));
     TORCH_CHECK(v.size(0) == 0 || v.stride(0) >= 1, who, ": column ", i, " needs a positive element stride");
     TORCH_CHECK(v.is_cuda() == onDevice, who, ": column ", i, " must live where the join runs");
     TORCH_CHECK(v.size(0) == rows, who, ": column ", i, " has ", v.size(0), " entries and does not cover the ", rows,
                 " outer rows");
-    c.col[i] = reinterpret_cast<const unsigned long long *>(v.data_ptr());
+    c.col[i] = v.data_ptr();
     c.stride[i] = v.size(0) ? (uint64_t)v.stride(0) : 1;
   }
   return c;
@@ -916,7 +971,8 @@ py::dict opBuildProbeGroupAgg(const at::Tensor &R, const at::Tensor &S, const at
   py::dict d;
   d["rows"] = rows;
   d["counts"] = accCount.narrow(0, 0, nR).to(at::kLong);
-  d["aggs"] = accAgg.narrow(1, 0, nR).contiguous();
+  d["aggs"] = accAgg.narrow(1, 0, nR).contiguous();  // (int64 words: the binary64 bits of a float column)
+  d["group_dtypes"] = groupWordDtypes(cols);
   d["matched_pairs"] = matched;
   d["unmatched_inner"] = zeros;
   return d;
@@ -2324,25 +2380,38 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           [](operators::HashJoin &j, std::shared_ptr<core::ExecContext> ctx, at::Tensor outerValues, uint64_t outerOffset,
              uint64_t outerGlobal) {
             // One kind=GROUP join that also sums outer_values per group: (result dict, rows [|R|, 3]).
-            // outer_values: 1-D int64, any positive element stride (a column view of a payload tensor).
+            // outer_values: 1-D int64 (or int32, float64, float32), any positive element stride (a column view of a payload tensor).
             TORCH_CHECK(j.getConfig().kind == core::JoinKind::Group, "join_group needs kind=GROUP, this join has kind=",
                         core::joinKindName(j.getConfig().kind));
             TORCH_CHECK(j.getConfig().materialize, "join_group needs materialize=True");
-            TORCH_CHECK(outerValues.dim() == 1 && outerValues.scalar_type() == at::kLong,
-                        "join_group: outer_values must be a 1-D int64 tensor");
+            // int32, float64 and float32 values (stride in elements of that dtype) take the aggregate path with one
+            // "sum" column: the sum word is int64 for int32 values, the bits of a binary64 for the float types.
+            uint32_t code = kernels::GROUP_I64;
+            TORCH_CHECK(outerValues.dim() == 1 && groupDtypeOf(outerValues.scalar_type(), code),
+                        "join_group: outer_values must be a 1-D int64 tensor (or int32, float64, float32); column 0 has ",
+                        outerValues.dim(), " dimension(s) and dtype ", groupTorchDtypeName(outerValues.scalar_type()));
             TORCH_CHECK(outerValues.size(0) == 0 || outerValues.stride(0) >= 1,
                         "join_group: outer_values need a positive element stride");
             TORCH_CHECK(outerValues.is_cuda() == j.context()->onDevice(), "join_group: outer_values must live where the join runs");
             TORCH_CHECK((uint64_t)outerValues.size(0) == outerGlobal, "join_group: outer_values has ", outerValues.size(0),
                         " entries, outer_global says ", outerGlobal);
             if (outerValues.is_cuda()) HIP_CHECK(hipDeviceSynchronize());  // values written on other streams
+            kernels::GroupColumns cols;
+            cols.n = 1;
+            cols.col[0] = outerValues.data_ptr();
+            cols.stride[0] = outerValues.size(0) ? (uint64_t)outerValues.stride(0) : 1;
+            cols.dtype[0] = code;
             operators::JoinResult r;
             {
               py::gil_scoped_release nogil;
-              r = j.joinGroup(ptr<uint64_t>(outerValues), outerOffset, outerGlobal,
-                              outerValues.size(0) ? (uint64_t)outerValues.stride(0) : 1);
+              if (code == kernels::GROUP_I64)
+                r = j.joinGroup(ptr<uint64_t>(outerValues), outerOffset, outerGlobal, cols.stride[0]);
+              else
+                r = j.joinGroupAgg(cols, outerOffset, outerGlobal);
             }
-            return py::make_tuple(resultToDict(r), groupRows(j));
+            py::dict d = resultToDict(r);
+            d["group_dtypes"] = groupWordDtypes(cols);
+            return py::make_tuple(d, groupRows(j));
           },
           py::arg("context"), py::arg("outer_values"), py::arg("outer_rid_offset") = 0, py::arg("outer_global_rows") = 0)
       .def(
@@ -2350,7 +2419,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           [](operators::HashJoin &j, std::shared_ptr<core::ExecContext> ctx, std::vector<at::Tensor> columns,
              std::vector<std::string> aggs, uint64_t outerOffset, uint64_t outerGlobal) {
             // One kind=GROUP join that aggregates 1 ... 4 outer value columns per group, each by "sum", "min" or
-            // "max": (result dict, rows [|R|, 2 + C] of (rid, count, agg_0, ...)).  Columns: 1-D int64, any
+            // "max": (result dict, rows [|R|, 2 + C] of (rid, count, agg_0, ...)).  Columns: 1-D int64, int32, float64 or float32, any
             // positive element stride each (views of one payload tensor, or separate tensors).
             TORCH_CHECK(j.getConfig().kind == core::JoinKind::Group, "join_group_agg needs kind=GROUP, this join has kind=",
                         core::joinKindName(j.getConfig().kind));
@@ -2367,7 +2436,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
               py::gil_scoped_release nogil;
               r = j.joinGroupAgg(cols, outerOffset, outerGlobal);
             }
-            return py::make_tuple(resultToDict(r), groupRows(j));
+            py::dict d = resultToDict(r);
+            d["group_dtypes"] = groupWordDtypes(cols);  // "int64", or "float64": the word holds binary64 bits
+            return py::make_tuple(d, groupRows(j));
           },
           py::arg("context"), py::arg("columns"), py::arg("aggs"), py::arg("outer_rid_offset") = 0,
           py::arg("outer_global_rows") = 0)

@@ -88,7 +88,11 @@ enum class ExchangeMode : int {
 //     4 outer value columns, each with its own SUM, signed MIN or signed MAX
 //     (HashJoin::joinGroupAgg; JoinConfig::groupColumns sizes the LDS tables;
 //     an empty group carries each aggregate's identity: 0, INT64_MAX,
-//     INT64_MIN; AVG is sum / count on the caller's side).  Copies of an inner
+//     INT64_MIN; AVG is sum / count on the caller's side).  Each column is
+//     int64, int32 (sign-extended, aggregated as int64), float64 or float32
+//     (aggregated as IEEE binary64: the row word holds its bits, an empty
+//     group +0.0, +inf, -inf; the sum in the order the updates land; NaN
+//     inputs unspecified) -- kernels::GroupDtype.  Copies of an inner
 //     key each get the key's full count and aggregates.  No pair is formed
 //     (kernels/group_join.hip).  local_matches /
 //     global_matches count the result rows (this rank's inner tuples);
@@ -142,7 +146,8 @@ struct JoinConfig {
   uint32_t rChunk = 0;          // max inner tuples per LDS table (0 = auto from LDS budget)
   uint32_t sChunk = 65536;      // max outer tuples per build/probe work item
   // kind Group: the most value columns a run may aggregate (1 ... 4; HashJoin::joinGroupAgg).  The automatic
-  // rChunk leaves room for this many 8-byte accumulators per LDS slot; a run with more columns is refused.
+  // rChunk leaves room for this many 8-byte accumulators per LDS slot (8 bytes whatever the column's element type:
+  // int64, int32, float64, float32); a run with more columns is refused.
   uint32_t groupColumns = 1;
   uint32_t chunks = 1;          // exchange pipeline slices per relation (>1: scatter(k+1) || all-to-all(k))
   bool checks = true;          // cheap always-on invariants (all tuples written, sizes)

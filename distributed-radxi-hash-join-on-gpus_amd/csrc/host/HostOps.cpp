@@ -536,7 +536,22 @@ uint64_t buildProbeGroupAgg(const kernels::BPArgs &a, const kernels::GroupColumn
   uint64_t pairs = 0;
   const uint64_t ridMask = a.keyShift >= 64 ? ~0ull : ((1ull << a.keyShift) - 1);
   for (uint32_t c = 0; c < cols.n; ++c)
-    std::fill(accAgg + c * accSlots, accAgg + (c + 1) * accSlots, (uint64_t)kernels::groupAggIdentity(cols.agg[c]));
+    std::fill(accAgg + c * accSlots, accAgg + (c + 1) * accSlots,
+              (uint64_t)kernels::groupAggIdentity(cols.agg[c], cols.dtype[c]));
+  // Column c's value of a row, widened to the accumulator's word: int32 sign-extended, float32 as binary64 bits.
+  auto load = [&](uint32_t c, uint64_t row) -> uint64_t {
+    const uint64_t idx = row * cols.stride[c];
+    switch (cols.dtype[c]) {
+      case kernels::GROUP_I32: return (uint64_t)(int64_t) static_cast<const int32_t *>(cols.col[c])[idx];
+      case kernels::GROUP_F32: {
+        const double d = (double)static_cast<const float *>(cols.col[c])[idx];
+        uint64_t bits;
+        std::memcpy(&bits, &d, 8);
+        return bits;
+      }
+      default: return static_cast<const uint64_t *>(cols.col[c])[idx];
+    }
+  };
   std::vector<uint64_t> bucket, next, rep;
   auto key = [&](const void *base, uint64_t i) -> uint64_t {
     if (a.wide) return static_cast<const data::Tuple *>(base)[i].key;
@@ -571,9 +586,15 @@ uint64_t buildProbeGroupAgg(const kernels::BPArgs &a, const kernels::GroupColumn
         const uint64_t rid =
             a.wide ? static_cast<const data::Tuple *>(a.S)[s].rid : (static_cast<const uint64_t *>(a.S)[s] & ridMask);
         for (uint32_t c = 0; c < cols.n; ++c) {
-          const uint64_t v = cols.col[c][(rid - cols.offset) * cols.stride[c]];
+          const uint64_t v = load(c, rid - cols.offset);
           uint64_t &acc = accAgg[c * accSlots + r];
-          if (cols.agg[c] == kernels::GROUP_MIN)
+          if (kernels::groupDtypeIsFloat(cols.dtype[c])) {  // binary64 on the bits, in sequential order
+            double x, y;
+            std::memcpy(&x, &acc, 8);
+            std::memcpy(&y, &v, 8);
+            x = cols.agg[c] == kernels::GROUP_MIN ? std::fmin(x, y) : cols.agg[c] == kernels::GROUP_MAX ? std::fmax(x, y) : x + y;
+            std::memcpy(&acc, &x, 8);
+          } else if (cols.agg[c] == kernels::GROUP_MIN)
             acc = (uint64_t)std::min((int64_t)acc, (int64_t)v);
           else if (cols.agg[c] == kernels::GROUP_MAX)
             acc = (uint64_t)std::max((int64_t)acc, (int64_t)v);

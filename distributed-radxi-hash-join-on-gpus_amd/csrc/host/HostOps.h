@@ -105,7 +105,9 @@ uint64_t groupEmit(const kernels::BPArgs &a, const uint32_t *accCount, const uin
 // The same with cols.n aggregated value columns (twins of kernels::bpGroupAgg /
 // groupEmitAgg): accAgg is column-major, accAgg[c * accSlots + r], and is set
 // here to every column's identity first (accCount is zeroed by the caller).
-// Rows are (rid, count, agg_0, ..., agg_{columns-1}).
+// Rows are (rid, count, agg_0, ..., agg_{columns-1}).  Typed columns
+// (cols.dtype) are widened as the kernel does -- int32 sign-extended, float32 to
+// binary64 -- and float columns aggregate as binary64 in sequential order.
 uint64_t buildProbeGroupAgg(const kernels::BPArgs &a, const kernels::GroupColumns &cols, uint32_t *accCount,
                             uint64_t *accAgg, uint64_t accSlots);
 uint64_t groupEmitAgg(const kernels::BPArgs &a, const uint32_t *accCount, const uint64_t *accAgg, uint64_t accSlots,

@@ -4,8 +4,10 @@
 // SUM ... GROUP BY the build side, without ever forming a pair.  With
 // aggregated value columns (GroupColumns): C = 1 ... 4 outer columns, each with
 // its own base pointer, stride and aggregate -- SUM (wraps), signed MIN or
-// signed MAX -- and rows (rid, count, agg_0, ..., agg_{C-1}).  AVG is sum /
-// count on the caller's side and is not built.
+// signed MAX -- and rows (rid, count, agg_0, ..., agg_{C-1}).  A column may
+// also be int32 (accumulated as int64), float64 or float32 (accumulated as
+// binary64, the row word holding its bits): the TYPED kernels below.  AVG is
+// sum / count on the caller's side and is not built.
 //
 //  * bpGroupKernel<LAYOUT, DIRECT, SUM> -- persistent grid over the BPItem
 //    list, geometry of bpOuterCountKernel (256 threads, 16 tuples per thread
@@ -66,12 +68,36 @@
 //    smax_x2 and no compare-and-swap loop for them (read once, hipcc of ROCm
 //    7; the only ds_cmpst is the slot claim of the build).
 //    No direct-addressed variant, for the reasons given for SUM above.  One
-//    column with SUM runs bpGroupKernel itself (bpGroupAgg() routes it).
+//    int64 column with SUM runs bpGroupKernel itself (bpGroupAgg() routes it).
+//  * bpGroupAggKernel<LAYOUT, C, TYPED> -- TYPED = false is the kernel above,
+//    for joins whose columns are all int64.  TYPED = true (any column int32,
+//    float64 or float32; one such column with SUM too): the element type is a
+//    kernel argument per column like the aggregate code, wave-uniform and
+//    branched on in scalar code.  The gather is a 4- or 8-byte non-temporal
+//    load of element row * stride (strides count elements of the column's own
+//    type) into a dword pair kept as loaded, so all C * G gathers are still
+//    issued before the first wait; the widening happens at the atomic: int32
+//    sign-extended, float32 converted to binary64 (v_cvt_f64_f32, exact).
+//    Accumulators stay 8 bytes per column and slot, so the LDS layout, the
+//    planned rChunk and G are those of TYPED = false.  Integer columns take
+//    the integer atomics above; float columns hold binary64 bits and take
+//    ds_add_f64 / ds_min_f64 / ds_max_f64 in LDS and global_atomic_add_f64 /
+//    min_f64 / max_f64 on the global accumulators (__hip_atomic_fetch_add /
+//    _min / _max on double, relaxed, workgroup and agent scope; read once in
+//    the assembly of this file: native, no compare-and-swap loop, no
+//    -munsafe-fp-atomics).  The hardware float atomics are valid on
+//    coarse-grained memory only: the global accumulators live in the engine's
+//    Arena or a torch tensor (hipMalloc) and must stay there.  Identities:
+//    +0.0, +inf, -inf (bits; groupAggIdentity).  A float SUM is the sum in the
+//    order the atomics land; MIN / MAX compare as IEEE numbers; NaN inputs and
+//    the order of -0.0 / +0.0 are unspecified.
 //  * groupEmitAggKernel<LAYOUT, C> -- groupEmitKernel<LAYOUT, SUM> with W = 2 +
 //    C words per row (4 to 6; one column takes groupEmitKernel's three): word q
 //    of the wave's run is stored by lane q % 64, so the stores stay consecutive
 //    8-byte words although W is no power of two.  Empty groups carry the
-//    identities the fill wrote.
+//    identities the fill wrote.  Both emit kernels only move 8-byte words
+//    (loads, lane shuffles, stores; no arithmetic on an aggregate), so the
+//    bits of a float column pass through unchanged.
 //
 // Count accumulators are u32: the caller refuses a global outer size of 2^32
 // or more (HashJoin, ops.build_probe_group).
@@ -92,6 +118,11 @@
 //   bpGroupAggKernel<compressed, C>  238 / 240 / 234 / 248 VGPRs for C = 1 / 2 / 3 / 4; 2 workgroups per CU
 //   bpGroupAggKernel<split, C>       186 / 188 / 182 / 196 VGPRs; 2 workgroups per CU
 //   bpGroupAggKernel<wide, C>        212 / 206 / 200 / 206 VGPRs; 2 workgroups per CU
+//   bpGroupAggKernel<*, C, TYPED>    the VGPRs of TYPED = false (split, C = 3: 183) and 5 - 17 more SGPRs (at most
+//                                    106); 2 workgroups per CU, G unchanged (16, 8, 4, 4; wide 8, 4, 2, 2).  The
+//                                    C = 4 instantiations keep 12 (compressed), 15 (split) and 13 (wide) SGPRs in
+//                                    VGPR lanes, split C = 3 keeps 2 (SGPR spills inside the VGPR counts above:
+//                                    no scratch, no VGPR spill)
 //   groupEmitAggKernel<*, C>         62-64 / 73-76 / 86-87 VGPRs for C = 2 / 3 / 4; 32 B LDS
 //   groupAggFillKernel               10 VGPRs, no LDS
 //   LDS of bpGroupKernel (dynamic, bpGroupLdsBytes): hashed 4-byte keys + counters 32 KiB + 64 B at the
@@ -353,6 +384,13 @@ constexpr int groupAggBatch(int layout, int c) {
 }
 
 // The aggregate code is wave-uniform (a kernel argument): one scalar branch per atomic.
+// TYPED: so is the column's type.  A floating-point accumulator holds the bits of a binary64 and takes the f64
+// atomics (add, IEEE min, IEEE max); the integer types take the forms below.
+template <bool TYPED>
+__device__ __forceinline__ void groupAggLdsT(unsigned long long *p, unsigned long long v, uint32_t agg, uint32_t dtype);
+template <bool TYPED>
+__device__ __forceinline__ void groupAggGlobalT(unsigned long long *p, unsigned long long v, uint32_t agg,
+                                                uint32_t dtype);
 __device__ __forceinline__ void groupAggLds(unsigned long long *p, unsigned long long v, uint32_t agg) {
   if (agg == GROUP_SUM)
     __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -370,18 +408,70 @@ __device__ __forceinline__ void groupAggGlobal(unsigned long long *p, unsigned l
     __hip_atomic_fetch_max(reinterpret_cast<long long *>(p), (long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+template <bool TYPED>
+__device__ __forceinline__ void groupAggLdsT(unsigned long long *p, unsigned long long v, uint32_t agg, uint32_t dtype) {
+  if (TYPED && groupDtypeIsFloat(dtype)) {
+    double *d = reinterpret_cast<double *>(p);
+    const double x = __longlong_as_double((long long)v);
+    if (agg == GROUP_SUM)
+      __hip_atomic_fetch_add(d, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else if (agg == GROUP_MIN)
+      __hip_atomic_fetch_min(d, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else
+      __hip_atomic_fetch_max(d, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  } else {
+    groupAggLds(p, v, agg);
+  }
+}
+template <bool TYPED>
+__device__ __forceinline__ void groupAggGlobalT(unsigned long long *p, unsigned long long v, uint32_t agg,
+                                                uint32_t dtype) {
+  if (TYPED && groupDtypeIsFloat(dtype)) {
+    double *d = reinterpret_cast<double *>(p);
+    const double x = __longlong_as_double((long long)v);
+    if (agg == GROUP_SUM)
+      __hip_atomic_fetch_add(d, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else if (agg == GROUP_MIN)
+      __hip_atomic_fetch_min(d, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else
+      __hip_atomic_fetch_max(d, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else {
+    groupAggGlobal(p, v, agg);
+  }
+}
+
+// TYPED gather: element idx of a column of 8- or 4-byte elements, as loaded, in two dwords; a 4-byte element leaves
+// `hi` alone (writing a zero there would have to wait for the gathers still in flight).  groupWiden turns the pair
+// into the accumulator's word when it is consumed, so no load is waited for early.
+__device__ __forceinline__ void groupGather(const void *col, uint64_t idx, uint32_t dtype, uint32_t &lo, uint32_t &hi) {
+  if (groupDtypeBytes(dtype) == 4) {
+    lo = __builtin_nontemporal_load(static_cast<const uint32_t *>(col) + idx);
+  } else {
+    const unsigned long long v = __builtin_nontemporal_load(static_cast<const unsigned long long *>(col) + idx);
+    lo = (uint32_t)v;
+    hi = (uint32_t)(v >> 32);
+  }
+}
+__device__ __forceinline__ unsigned long long groupWiden(uint32_t lo, uint32_t hi, uint32_t dtype) {
+  if (dtype == GROUP_I32) return (unsigned long long)(long long)(int32_t)lo;                          // sign-extended
+  if (dtype == GROUP_F32) return (unsigned long long)__double_as_longlong((double)__uint_as_float(lo));  // exact
+  return ((unsigned long long)hi << 32) | lo;
+}
+
 // Every column's identity over its accSlots accumulators (column-major).
 __global__ __launch_bounds__(GJ_T) void groupAggFillKernel(GroupColumns cols, unsigned long long *__restrict__ accAgg,
                                                           uint64_t accSlots) {
   for (uint32_t c = 0; c < cols.n; ++c) {
-    const unsigned long long ident = groupAggIdentity(cols.agg[c]);
+    const unsigned long long ident = groupAggIdentity(cols.agg[c], cols.dtype[c]);
     for (uint64_t i = (uint64_t)blockIdx.x * GJ_T + threadIdx.x; i < accSlots; i += (uint64_t)gridDim.x * GJ_T)
       accAgg[c * accSlots + i] = ident;
   }
 }
 
 // bpGroupKernel<LAYOUT, false, true> with C accumulators per slot, each with its own column and aggregate.
-template <int LAYOUT, int C>
+// TYPED = false: every column is int64 (the code of the kernel before the typed columns); TYPED = true: each
+// column has its own element type as well (cols.dtype), branched on in scalar code like the aggregate.
+template <int LAYOUT, int C, bool TYPED>
 __global__ __launch_bounds__(GJ_T, 2) void bpGroupAggKernel(BPArgs a, const BPItem *__restrict__ items,
                                                             const uint32_t *__restrict__ nItemsPtr, uint32_t capacity,
                                                             GroupColumns cols, uint32_t *accCount,
@@ -392,7 +482,7 @@ __global__ __launch_bounds__(GJ_T, 2) void bpGroupAggKernel(BPArgs a, const BPIt
   constexpr K EMPTY = LAYOUT == MK_WIDE ? (K)GJ_EMPTY64 : (K)GJ_EMPTY32;
   constexpr uint32_t BATCH = GJ_T * GJ_K;
   constexpr bool PRE_RID = LAYOUT != MK_WIDE;  // wide tuples read their rid when a slot was found
-  constexpr int G = groupAggBatch(LAYOUT, C);
+  constexpr int G = groupAggBatch(LAYOUT, C);  // (TYPED holds the values as loaded: no more VGPRs, the same G)
   const uint64_t maxSlots = groupMaxSlots(a.rChunk);
   // [agg u64 x slots] x C (column-major) [key x slots][count u32 x slots][8 x u64 reduction words]
   unsigned long long *aggs = reinterpret_cast<unsigned long long *>(smem);
@@ -404,7 +494,7 @@ __global__ __launch_bounds__(GJ_T, 2) void bpGroupAggKernel(BPArgs a, const BPIt
   const uint64_t ridMask = a.keyShift >= 64 ? ~0ull : ((1ull << a.keyShift) - 1);
   unsigned long long ident[C];
 #pragma unroll
-  for (int c = 0; c < C; ++c) ident[c] = groupAggIdentity(cols.agg[c]);
+  for (int c = 0; c < C; ++c) ident[c] = groupAggIdentity(cols.agg[c], TYPED ? cols.dtype[c] : (uint32_t)GROUP_I64);
   unsigned long long matches = 0;
   for (uint32_t w = blockIdx.x; w < nItems; w += gridDim.x) {
     const BPItem it = items[w];
@@ -479,7 +569,8 @@ __global__ __launch_bounds__(GJ_T, 2) void bpGroupAggKernel(BPArgs a, const BPIt
             if (slot[j] != GJ_NONE)
               wrid[j] = reinterpret_cast<const unsigned long long *>(a.S)[2 * (sb + b0 + (g0 + j) * GJ_T + t) + 1];
         }
-        unsigned long long val[C][G];
+        unsigned long long val[TYPED ? 1 : C][TYPED ? 1 : G];
+        uint32_t vlo[TYPED ? C : 1][TYPED ? G : 1], vhi[TYPED ? C : 1][TYPED ? G : 1];  // TYPED: as loaded
 #pragma unroll
         for (int j = 0; j < G; ++j) {
           if (slot[j] != GJ_NONE) {  // a tuple that found no slot forms no address
@@ -488,7 +579,13 @@ __global__ __launch_bounds__(GJ_T, 2) void bpGroupAggKernel(BPArgs a, const BPIt
             else rid = LAYOUT == MK_COMPRESSED ? ((uint64_t)rr[g0 + j] & ridMask) : (uint64_t)rr[g0 + j];
             const uint64_t row = rid - cols.offset;
 #pragma unroll
-            for (int c = 0; c < C; ++c) val[c][j] = __builtin_nontemporal_load(cols.col[c] + row * cols.stride[c]);
+            for (int c = 0; c < C; ++c) {
+              if constexpr (TYPED)
+                groupGather(cols.col[c], row * cols.stride[c], cols.dtype[c], vlo[c][j], vhi[c][j]);
+              else
+                val[c][j] = __builtin_nontemporal_load(static_cast<const unsigned long long *>(cols.col[c]) +
+                                                       row * cols.stride[c]);
+            }
           }
         }
 #pragma unroll
@@ -496,7 +593,13 @@ __global__ __launch_bounds__(GJ_T, 2) void bpGroupAggKernel(BPArgs a, const BPIt
           if (slot[j] != GJ_NONE) {
             atomicAdd(&cnt[slot[j]], 1u);
 #pragma unroll
-            for (int c = 0; c < C; ++c) groupAggLds(&aggs[c * maxSlots + slot[j]], val[c][j], cols.agg[c]);
+            for (int c = 0; c < C; ++c) {
+              if constexpr (TYPED)
+                groupAggLdsT<true>(&aggs[c * maxSlots + slot[j]], groupWiden(vlo[c][j], vhi[c][j], cols.dtype[c]),
+                                   cols.agg[c], cols.dtype[c]);
+              else
+                groupAggLds(&aggs[c * maxSlots + slot[j]], val[c][j], cols.agg[c]);
+            }
           }
         }
       }
@@ -518,8 +621,13 @@ __global__ __launch_bounds__(GJ_T, 2) void bpGroupAggKernel(BPArgs a, const BPIt
             matches += c0;
             atomicAdd(&accCount[rb + idx], c0);
 #pragma unroll
-            for (int c = 0; c < C; ++c)
-              groupAggGlobal(&accAgg[c * accSlots + rb + idx], aggs[c * maxSlots + h], cols.agg[c]);
+            for (int c = 0; c < C; ++c) {
+              if constexpr (TYPED)
+                groupAggGlobalT<true>(&accAgg[c * accSlots + rb + idx], aggs[c * maxSlots + h], cols.agg[c],
+                                      cols.dtype[c]);
+              else
+                groupAggGlobal(&accAgg[c * accSlots + rb + idx], aggs[c * maxSlots + h], cols.agg[c]);
+            }
           }
         }
       }
@@ -744,8 +852,11 @@ void groupEmit(const BPArgs &args, const MarkUnit *units, const uint32_t *nUnits
 static void groupColumnsCheck(const GroupColumns &cols, const char *who) {
   HJ_CHECK(cols.n >= 1 && cols.n <= GROUP_MAX_COLUMNS, "%s: %u value columns (1 to %u)", who, cols.n, GROUP_MAX_COLUMNS);
   for (uint32_t c = 0; c < cols.n; ++c)
-    HJ_CHECK(cols.col[c] && cols.stride[c] >= 1 && cols.agg[c] <= GROUP_MAX,
-             "%s: column %u needs values, a stride >= 1 and an aggregate (sum, min, max)", who, c);
+    HJ_CHECK(cols.col[c] && cols.stride[c] >= 1 && cols.agg[c] <= GROUP_MAX && cols.dtype[c] <= GROUP_DTYPE_MAX &&
+                 reinterpret_cast<uintptr_t>(cols.col[c]) % groupDtypeBytes(cols.dtype[c]) == 0,
+             "%s: column %u needs aligned values, a stride >= 1, an aggregate (sum, min, max) and an element type "
+             "(int64, int32, float64, float32)",
+             who, c);
 }
 
 void groupAggFill(const GroupColumns &cols, unsigned long long *accAgg, uint64_t accSlots, hipStream_t s) {
@@ -762,8 +873,10 @@ void bpGroupAgg(const BPArgs &args, const BPItem *items, const uint32_t *nItems,
                 hipStream_t s) {
   if (capacity == 0) return;
   groupColumnsCheck(cols, "bpGroupAgg");
-  if (cols.n == 1 && cols.agg[0] == GROUP_SUM) {  // the single-column kernel (identity 0: the fill zeroed it)
-    bpGroup(args, items, nItems, capacity, cols.col[0], cols.offset, cols.stride[0], accCount, accAgg, s);
+  const bool typed = groupColumnsTyped(cols);
+  if (cols.n == 1 && cols.agg[0] == GROUP_SUM && !typed) {  // the single-column kernel (identity 0: the fill zeroed it)
+    bpGroup(args, items, nItems, capacity, static_cast<const unsigned long long *>(cols.col[0]), cols.offset,
+            cols.stride[0], accCount, accAgg, s);
     return;
   }
   const BPArgs a = groupArgs(args);
@@ -778,9 +891,12 @@ void bpGroupAgg(const BPArgs &args, const BPItem *items, const uint32_t *nItems,
   HJ_CHECK(a.result && accCount && accAgg, "bpGroupAgg: needs the pair counter and the accumulators");
   const uint32_t perCu = (uint32_t)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / lds));
   const uint32_t blocks = std::min<uint32_t>(capacity, 256 * perCu);
-#define HJ_GJ_AGG(LAYOUT, C)                                                                                        \
-  hipLaunchKernelGGL((bpGroupAggKernel<LAYOUT, C>), dim3(blocks), dim3(GJ_T), lds, s, a, items, nItems, capacity, cols, \
-                     accCount, accAgg, accSlots)
+#define HJ_GJ_AGG_T(LAYOUT, C, TYPED)                                                                          \
+  hipLaunchKernelGGL((bpGroupAggKernel<LAYOUT, C, TYPED>), dim3(blocks), dim3(GJ_T), lds, s, a, items, nItems, capacity, \
+                     cols, accCount, accAgg, accSlots)
+#define HJ_GJ_AGG(LAYOUT, C)            \
+  if (typed) HJ_GJ_AGG_T(LAYOUT, C, true); \
+  else HJ_GJ_AGG_T(LAYOUT, C, false)
 #define HJ_GJ_AGG_C(LAYOUT)                   \
   switch (cols.n) {                           \
     case 1: HJ_GJ_AGG(LAYOUT, 1); break;      \
@@ -795,6 +911,7 @@ void bpGroupAgg(const BPArgs &args, const BPItem *items, const uint32_t *nItems,
   }
 #undef HJ_GJ_AGG_C
 #undef HJ_GJ_AGG
+#undef HJ_GJ_AGG_T
   HIP_CHECK_LAUNCH();
 }
 

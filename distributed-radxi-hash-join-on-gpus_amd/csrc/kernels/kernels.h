@@ -507,22 +507,46 @@ struct GroupValues {
   uint64_t strideWords = 1;
 };
 // Outer value columns of a group join with aggregates (HashJoin::setGroupColumns):
-// n = 1 ... GROUP_MAX_COLUMNS columns, each a 1-D int64 view with its own base
-// pointer, positive element stride and aggregate; column c's value of rid r is
-// col[c][(r - offset) * stride[c]], rids [offset, offset + rows).  SUM wraps;
-// MIN and MAX compare as signed int64.  Passed to the kernels by value.
+// n = 1 ... GROUP_MAX_COLUMNS columns, each a 1-D view with its own base
+// pointer, element type (GroupDtype), positive element stride (in elements of
+// that type) and aggregate; column c's value of rid r is element
+// (r - offset) * stride[c] of col[c], rids [offset, offset + rows).
+// Accumulators and row words are 8 bytes whatever the element type: int64 and
+// int32 (sign-extended on load) accumulate as int64 -- SUM wraps, MIN and MAX
+// compare signed; float64 and float32 (converted on load, exactly) accumulate
+// as IEEE binary64, the word holding its bit pattern -- SUM in the order the
+// updates land, MIN and MAX as IEEE numbers; a NaN input gives an unspecified
+// result, and so does the order of -0.0 and +0.0 in MIN / MAX.  Passed to the
+// kernels by value.
 constexpr uint32_t GROUP_MAX_COLUMNS = 4;
 enum GroupAgg : uint32_t { GROUP_SUM = 0, GROUP_MIN = 1, GROUP_MAX = 2 };
+// Bit 0: 4-byte elements; bit 1: floating point.
+enum GroupDtype : uint32_t { GROUP_I64 = 0, GROUP_I32 = 1, GROUP_F64 = 2, GROUP_F32 = 3, GROUP_DTYPE_MAX = 3 };
 struct GroupColumns {
-  const unsigned long long *col[GROUP_MAX_COLUMNS] = {nullptr, nullptr, nullptr, nullptr};
+  const void *col[GROUP_MAX_COLUMNS] = {nullptr, nullptr, nullptr, nullptr};
   uint64_t stride[GROUP_MAX_COLUMNS] = {1, 1, 1, 1};
   uint32_t agg[GROUP_MAX_COLUMNS] = {GROUP_SUM, GROUP_SUM, GROUP_SUM, GROUP_SUM};
+  uint32_t dtype[GROUP_MAX_COLUMNS] = {GROUP_I64, GROUP_I64, GROUP_I64, GROUP_I64};
   uint32_t n = 0;
   uint64_t offset = 0;
   uint64_t rows = 0;
 };
-// What an aggregate of no value is: 0, INT64_MAX, INT64_MIN (the rows of empty groups carry it).
-HJ_HD unsigned long long groupAggIdentity(uint32_t agg) {
+HJ_HD bool groupDtypeIsFloat(uint32_t dtype) { return (dtype & 2u) != 0; }
+HJ_HD uint32_t groupDtypeBytes(uint32_t dtype) { return (dtype & 1u) ? 4u : 8u; }
+inline const char *groupDtypeName(uint32_t dtype) {
+  return dtype == GROUP_I64 ? "int64" : dtype == GROUP_I32 ? "int32" : dtype == GROUP_F64 ? "float64" : "float32";
+}
+// True when any column is not int64: those joins run the typed kernels.
+inline bool groupColumnsTyped(const GroupColumns &cols) {
+  for (uint32_t c = 0; c < cols.n; ++c)
+    if (cols.dtype[c] != GROUP_I64) return true;
+  return false;
+}
+// What an aggregate of no value is (the rows of empty groups carry it): 0, INT64_MAX, INT64_MIN for the integer
+// types; the bits of +0.0, +inf, -inf for the floating-point types.
+HJ_HD unsigned long long groupAggIdentity(uint32_t agg, uint32_t dtype = GROUP_I64) {
+  if (groupDtypeIsFloat(dtype))
+    return agg == GROUP_MIN ? 0x7FF0000000000000ull : agg == GROUP_MAX ? 0xFFF0000000000000ull : 0ull;
   return agg == GROUP_MIN ? 0x7FFFFFFFFFFFFFFFull : agg == GROUP_MAX ? 0x8000000000000000ull : 0ull;
 }
 size_t bpLdsBytes(const BPArgs &a);
@@ -673,11 +697,16 @@ void groupEmit(const BPArgs &a, const MarkUnit *units, const uint32_t *nUnits, u
                unsigned long long *out, uint64_t outCapacity, hipStream_t s);
 
 // Group joins with aggregates: cols.n = 1 ... GROUP_MAX_COLUMNS value columns,
-// each summed (wrapping), or reduced to its signed minimum or maximum.
+// each int64, int32, float64 or float32 (GroupDtype) and each summed, or
+// reduced to its minimum or maximum (see GroupColumns for the arithmetic).
 // accCount as bpGroup; accAgg is column-major, accAgg[c * accSlots + position],
-// and must hold every column's identity before the launch (groupAggFill; the
-// accumulators of MIN and MAX cannot be cleared by a memset).  One column with
-// GROUP_SUM runs bpGroup itself.  An LDS request above 160 KiB is refused.
+// 8 bytes per accumulator whatever the column's type (int64, or the bits of a
+// binary64), and must hold every column's identity before the launch
+// (groupAggFill; the accumulators of MIN and MAX cannot be cleared by a
+// memset).  accAgg must be coarse-grained device memory (hipMalloc): the
+// floating-point atomics are hardware atomics only there.  One int64 column
+// with GROUP_SUM runs bpGroup itself; columns that are all int64 run the
+// integer-only kernels.  An LDS request above 160 KiB is refused.
 void groupAggFill(const GroupColumns &cols, unsigned long long *accAgg, uint64_t accSlots, hipStream_t s);
 void bpGroupAgg(const BPArgs &a, const BPItem *items, const uint32_t *nItems, uint32_t capacity,
                 const GroupColumns &cols, uint32_t *accCount, unsigned long long *accAgg, uint64_t accSlots,

@@ -893,6 +893,10 @@ void HashJoin::setGroupColumns(const kernels::GroupColumns &c) {
   for (uint32_t i = 0; i < c.n; ++i) {
     JOIN_ASSERT(c.col[i] && c.stride[i] >= 1, "HashJoin", "join_group_agg: column %u needs values and a positive stride", i);
     JOIN_ASSERT(c.agg[i] <= kernels::GROUP_MAX, "HashJoin", "join_group_agg: column %u has no aggregate %u", i, c.agg[i]);
+    JOIN_ASSERT(c.dtype[i] <= kernels::GROUP_DTYPE_MAX, "HashJoin",
+                "join_group_agg: column %u has no element type %u (int64, int32, float64, float32)", i, c.dtype[i]);
+    JOIN_ASSERT(reinterpret_cast<uintptr_t>(c.col[i]) % kernels::groupDtypeBytes(c.dtype[i]) == 0, "HashJoin",
+                "join_group_agg: column %u (%s) is not aligned to its element size", i, kernels::groupDtypeName(c.dtype[i]));
   }
   JOIN_ASSERT(ridLo[1] > ridHi[1] || (ridLo[1] >= c.offset && ridHi[1] - c.offset < c.rows), "HashJoin",
               "join_group_agg: outer values [%lu, %lu) do not cover this rank's outer rids [%lu, %lu]",
@@ -1071,10 +1075,10 @@ JoinResult HashJoin::runImpl() {
 
   // --------------------------------------------- local pass and build/probe
   LocalPhase local(env, localOverflowed, hasSink && (canFuseRows() || canFuseKindRows()) ? &sink : nullptr);
-  kernels::GroupValues oneSum;  // a single SUM column takes the single-column kernels
+  kernels::GroupValues oneSum;  // a single int64 SUM column takes the single-column kernels
   if (hasGroupColumns && plan.kind == core::JoinKind::Group) {
-    if (groupColumns.n == 1 && groupColumns.agg[0] == kernels::GROUP_SUM) {
-      oneSum.values = reinterpret_cast<const uint64_t *>(groupColumns.col[0]);
+    if (groupColumns.n == 1 && groupColumns.agg[0] == kernels::GROUP_SUM && !kernels::groupColumnsTyped(groupColumns)) {
+      oneSum.values = static_cast<const uint64_t *>(groupColumns.col[0]);
       oneSum.offset = groupColumns.offset;
       oneSum.rows = groupColumns.rows;
       oneSum.strideWords = groupColumns.stride[0];

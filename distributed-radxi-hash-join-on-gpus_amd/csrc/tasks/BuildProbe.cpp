@@ -371,7 +371,10 @@ void BuildProbe::executeOuter() {
 // a second run()) starts clean.  With aggregated value columns (groupColumns)
 // there are C accumulators per position, column-major, and every run first
 // writes their identities (kernels::groupAggFill; the host twin does the same):
-// INT64_MAX and INT64_MIN are no memset pattern.
+// INT64_MAX and INT64_MIN are no memset pattern, nor are the +inf / -inf of a
+// float column (groupColumns carries each column's element type to the kernels
+// and the host twin).  The accumulators come from the Arena (hipMalloc,
+// coarse-grained), where the hardware float atomics of typed columns are valid.
 void BuildProbe::executeGroup() {
   const bool dev = ctx->onDevice();
   const uint32_t C = groupColumns ? groupColumns->n : 0;

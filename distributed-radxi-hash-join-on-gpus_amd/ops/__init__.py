@@ -102,7 +102,8 @@ def build_probe_group(R, S, part_r, part_s, frag_shift: int, key_shift: int, wid
     of (inner rid, count, sum) with ``values``, a 1-D int64 tensor with ``values[rid - rid_offset]`` the value
     of outer tuple ``rid``; any positive element stride), ``matched_pairs`` (the sum of the counts),
     ``unmatched_inner`` (groups with count 0) and the raw accumulators ``counts`` / ``sums`` (int64, by position
-    of R)."""
+    of R).  int32, float64 or float32 ``values`` run ``build_probe_group_agg`` with one ``"sum"`` column (``sums``
+    then holds binary64 bits for the float dtypes, and ``group_dtypes`` says so)."""
     return _C().ops.build_probe_group(R, S, part_r, part_s, frag_shift, key_shift, wide, r_chunk, s_chunk, values,
                                       rid_offset)
 
@@ -114,7 +115,9 @@ def build_probe_group_agg(R, S, part_r, part_s, frag_shift: int, key_shift: int,
     (int64, wraps), ``"min"``, ``"max"`` (signed) per column.  ``rows`` (int64 ``[|R|, 2 + C]`` of (inner rid, count,
     agg_0, ...); a tuple without a partner has count 0 and each aggregate's identity: 0, INT64_MAX, INT64_MIN),
     ``matched_pairs``, ``unmatched_inner`` and the raw accumulators ``counts`` (``[|R|]``) and ``aggs``
-    (``[C, |R|]``), by position of R."""
+    (``[C, |R|]``), by position of R.  Columns may also be int32, float64 or float32 (see ``group_join_agg``):
+    ``aggs`` and ``rows`` stay int64 and hold binary64 bits for float columns (identities ``+0.0``, ``+inf``,
+    ``-inf``); ``group_dtypes`` lists the row-word dtype per column, ``"int64"`` or ``"float64"``."""
     return _C().ops.build_probe_group_agg(R, S, part_r, part_s, frag_shift, key_shift, wide, r_chunk, s_chunk,
                                           list(columns), [str(a) for a in aggs], rid_offset)
 
@@ -280,7 +283,13 @@ def group_join_sum(inner: torch.Tensor, outer: torch.Tensor, values: torch.Tenso
                    config=None) -> torch.Tensor:
     """int64 [|inner|, 3]: ``(inner rid, count, sum)`` per inner tuple, sum = the int64 (wrapping) sum of
     ``values[rid - rid_offset]`` over the outer tuples with its key.  ``values`` is a 1-D int64 tensor of any
-    positive element stride (a column view such as ``S_rows[:, 2]`` is read in place)."""
+    positive element stride (a column view such as ``S_rows[:, 2]`` is read in place).
+
+    ``values`` may also be int32 (sign-extended, summed as int64), float64 or float32 (converted exactly, summed
+    as IEEE binary64): the stride then counts elements of that dtype, and for the float dtypes the sum word holds
+    the bit pattern of the binary64 sum (``group_agg_values(rows, 0, values)`` views it as float64).  A float sum
+    is taken in the order the updates land -- exact whenever every partial sum is representable, otherwise
+    within the usual rounding bound; an empty group carries ``+0.0``.  NaN inputs give an unspecified result."""
     return _group_join(inner, outer, values, rid_offset, config)
 
 
@@ -290,7 +299,17 @@ def group_join_agg(inner: torch.Tensor, outer: torch.Tensor, columns, aggs, rid_
     with its key.  ``columns``: C = 1 ... 4 1-D int64 tensors with ``column[rid - rid_offset]`` the value of outer
     tuple ``rid`` (views such as ``S_rows[:, 1]`` are read in place; the same view may come twice); ``aggs``: one
     of ``"sum"`` (wraps), ``"min"``, ``"max"`` (signed) per column.  A tuple without a partner has count 0 and each
-    aggregate's identity (0, INT64_MAX, INT64_MIN).  AVG is ``sum / count`` on the caller's side."""
+    aggregate's identity (0, INT64_MAX, INT64_MIN).  AVG is ``sum / count`` on the caller's side.
+
+    Each column may independently be int64, int32, float64 or float32; its stride counts elements of its own
+    dtype (``rows32[:, 3]`` of an ``[n, 8]`` int32 tensor is read in place with 4-byte loads).  int32 values are
+    sign-extended and aggregate as int64 (a sum cannot wrap).  float64 / float32 values aggregate as IEEE
+    binary64 (float32 converts exactly) and the row word holds the binary64 bit pattern -- read it with
+    ``group_agg_values(rows, c, column)``.  Float identities: ``+0.0`` (sum), ``+inf`` (min), ``-inf`` (max).  A
+    float sum is the sum in whatever order the updates land: exact whenever every partial sum is representable,
+    otherwise within the usual rounding bound.  Float MIN / MAX compare as IEEE numbers; NaN inputs give an
+    unspecified result, and so does the relative order of ``-0.0`` and ``+0.0``.  With a float64 sum, AVG is one
+    division on the caller's side.  Any other dtype (float16, bool, uint8, ...) is refused."""
     C = _C()
     cfg = config or C.JoinConfig()
     cfg.kind = C.JoinKind.GROUP
@@ -304,6 +323,18 @@ def group_join_agg(inner: torch.Tensor, outer: torch.Tensor, columns, aggs, rid_
     j = C.HashJoin(R, S, ctx, cfg)
     _, rows = j.join_group_agg(ctx, list(columns), [str(a) for a in aggs], rid_offset, outer.shape[0])
     return rows
+
+
+def group_agg_values(rows: torch.Tensor, c: int, like=None) -> torch.Tensor:
+    """Aggregate column ``c`` of group-join rows (``rows[:, 2 + c]``) as a 1-D tensor: int64, or -- when ``like``
+    is a float32 / float64 tensor or dtype, i.e. the value column was a float column -- float64, a bit-level view
+    of the same words (no conversion pass, no copy)."""
+    assert rows.dim() == 2 and rows.dtype == torch.int64 and 0 <= c < rows.shape[1] - 2, (rows.shape, rows.dtype, c)
+    col = rows[:, 2 + c]
+    dtype = like.dtype if isinstance(like, torch.Tensor) else like
+    if dtype in (torch.float32, torch.float64):
+        return col.view(torch.float64)
+    return col
 
 
 def _kind_join_rows(inner, outer, kind: str, inner_rows, outer_rows, rid_offset: int, config=None) -> torch.Tensor:

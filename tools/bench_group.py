@@ -3,6 +3,7 @@
 them, same relations, one process on one GPU.
 
     python tools/bench_group.py [--workload gpu_128m] [--scale 1.0] [--steps 5] [--warmup 2]
+                                [--value-dtype int64|int32|float64|float32]
 
 Runs the workload's Zipf-outer variant (theta 0.75 over the inner key domain)
 and prints one JSON line per configuration -- join_ms, the device build/probe
@@ -29,7 +30,19 @@ iterations:
 Every result is checked against oracle counts (sorted outer keys, searchsorted
 of the inner keys), sums (wrapping prefix sums of the values in outer key
 order) and minima / maxima (scatter_reduce_ over the matching outer tuples).
-The last lines compare the medians: c and d must lie below a by more than a's
+--value-dtype generates the value columns in that dtype (still strided views of
+one payload tensor): int32 over the whole range, float64 as k / 8 with |k| < 2^30
+and float32 as k / 8 with |k| < 2^20, so that every float sum is exact in
+binary64 whatever the order and the check stays exact equality.  Integer columns
+accumulate as int64, float columns as binary64; the torch baselines gather in the
+column's dtype, widen the gathered values the same way and reduce with
+index_add_ / scatter_reduce_.  For the float dtypes the oracle uses no float
+scatter operation (sums from integer prefix sums of k, minima / maxima from
+int64 scatter_reduce_ on an order-preserving image of the bits), and the torch
+reductions of a (its sum and g's [sum, min, max] baseline) run only with
+--float-torch-baseline; without it a's torch_sum / total_sum / *_sum_min_max
+fields and the comparisons built on them are null
+(profiles/group_typed/README.md says why).  The last lines compare the medians: c and d must lie below a by more than a's
 own min-to-max spread; c / b, f / e and g against a's torch route are reported.
 """
 import argparse
@@ -51,6 +64,9 @@ def main():
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--value-dtype", default="int64", choices=["int64", "int32", "float64", "float32"])
+    ap.add_argument("--float-torch-baseline", action="store_true",
+                    help="float dtypes: also time torch's float64 index_add_ / scatter_reduce_ (see the module docstring)")
     a = ap.parse_args()
     assert a.steps >= 5, "at least 5 timed steps per configuration"
 
@@ -68,9 +84,27 @@ def main():
     R, S = C.Relation(G_R, G_R, "device", 0), C.Relation(G_S, G_S, "device", 0)
     R.generate(inner, 0)
     S.generate(outer, 0)
-    values = torch.randint(-2**40, 2**40, (G_S,), device="cuda", generator=torch.Generator("cuda").manual_seed(9))
+    vdt = getattr(torch, a.value_dtype)
+    is_float = vdt.is_floating_point
+    acc = torch.float64 if is_float else torch.int64  # what the accumulators and the row words hold
+    IDENT = {"min": float("inf"), "max": float("-inf")} if is_float else {"min": 2**63 - 1, "max": -2**63}
+
+    def gen(shape, seed):  # int64 as ever; the other dtypes as the module docstring says
+        span = {"int64": 2**40, "int32": 2**31, "float64": 2**30, "float32": 2**20}[a.value_dtype]
+        k = torch.randint(-span, span, shape, device="cuda", generator=torch.Generator("cuda").manual_seed(seed))
+        return (k.to(vdt) / 8) if is_float else k.to(vdt)
+
+    torch_reduce = not is_float or a.float_torch_baseline
+
+    def ordered(b):  # int64 bits of binary64 values <-> int64 keys in the values' order (its own inverse)
+        return torch.where(b < 0, b ^ 0x7FFFFFFFFFFFFFFF, b)
+
+    def bits(t):  # the int64 words of an accumulator tensor
+        return t.view(torch.int64) if t.dtype == torch.float64 else t
+
+    values = gen((G_S,), 9)
     # Two more value columns: with `values` the columns 1, 2, 3 of one [n, 4] payload tensor, read in place.
-    payload = torch.randint(-2**40, 2**40, (G_S, 4), device="cuda", generator=torch.Generator("cuda").manual_seed(10))
+    payload = gen((G_S, 4), 10)
     payload[:, 1] = values
     cols = [payload[:, 1], payload[:, 2], payload[:, 3]]
 
@@ -79,30 +113,37 @@ def main():
     sk, order = torch.sort(St[:, 0])
     lo = torch.searchsorted(sk, Rt[:, 0].contiguous(), right=False)
     hi = torch.searchsorted(sk, Rt[:, 0].contiguous(), right=True)
-    prefix = torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda"), torch.cumsum(values[St[:, 1][order]], 0)])
     want_counts = torch.empty(G_R, dtype=torch.int64, device="cuda")
-    want_sums = torch.empty(G_R, dtype=torch.int64, device="cuda")
     want_counts[Rt[:, 1]] = hi - lo
-    want_sums[Rt[:, 1]] = prefix[hi] - prefix[lo]  # int64 wraps both ways
     pairs_total, empty = int(want_counts.sum()), int((want_counts == 0).sum())
-    del prefix
 
-    def want_agg(col, how):  # by inner rid, from the outer tuples in key order
-        v = col[St[:, 1][order]]
+    def want_agg(col, how):  # by inner rid, from the outer tuples in key order; dtype `acc`
+        v = col[St[:, 1][order]].to(acc)
         if how == "sum":
+            if is_float:  # integer prefix sums of k = 8 v: exact, and no float atomics
+                k = (v * 8).to(torch.int64)
+                assert torch.equal(k.to(acc) / 8, v)
+                v = k
             p = torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda"), torch.cumsum(v, 0)])
-            per_pos = p[hi] - p[lo]
+            per_pos = p[hi] - p[lo]  # int64 wraps both ways
+            if is_float:
+                assert int(per_pos.abs().max()) < 2**53
+                per_pos = per_pos.to(acc) / 8
         else:
             seg = torch.repeat_interleave(torch.arange(G_R, device="cuda"), hi - lo)  # inner position of every pair
             src = v[torch.repeat_interleave(lo, hi - lo) + torch.arange(seg.numel(), device="cuda") -
                     torch.repeat_interleave(torch.cumsum(hi - lo, 0) - (hi - lo), hi - lo)]
-            ident = 2**63 - 1 if how == "min" else -2**63
-            per_pos = torch.full((G_R,), ident, dtype=torch.int64, device="cuda").scatter_reduce_(
-                0, seg, src, "amin" if how == "min" else "amax", include_self=True)
-        out = torch.empty(G_R, dtype=torch.int64, device="cuda")
+            ident = torch.tensor([IDENT[how]], dtype=acc, device="cuda")
+            if is_float:  # int64 scatter_reduce_ on keys ordered as the values
+                src, ident = ordered(src.view(torch.int64)), ordered(ident.view(torch.int64))
+            per_pos = ident.repeat(G_R).scatter_reduce_(0, seg, src, "amin" if how == "min" else "amax", include_self=True)
+            if is_float:
+                per_pos = ordered(per_pos).view(acc)
+        out = torch.empty(G_R, dtype=acc, device="cuda")
         out[Rt[:, 1]] = per_pos
         return out
 
+    want_sums = want_agg(values, "sum")
     want = {(c, how): want_agg(cols[c], how) for c, how in ((0, "sum"), (1, "sum"), (2, "sum"), (0, "min"), (1, "min"),
                                                              (2, "max"))}
     assert torch.equal(want[(0, "sum")], want_sums)
@@ -116,7 +157,7 @@ def main():
         return C.HashJoin(R, S, ctx, cfg)
 
     def report(name, what, j, runs, extra=None):
-        line = {"workload": wl.name, "config": name, "what": what, "inner": G_R, "outer": G_S,
+        line = {"workload": wl.name, "config": name, "what": what, "value_dtype": a.value_dtype, "inner": G_R, "outer": G_S,
                 "join_ms": _spread([r["join_ms"] for r in runs]),
                 "dev_build_probe_ms": _spread([r["dev_build_probe_ms"] for r in runs]),
                 "matched_pairs": runs[-1]["matched_pairs"], "unmatched_inner": runs[-1]["unmatched_inner"],
@@ -146,39 +187,49 @@ def main():
         rid, srid = pairs[:, 0][m], pairs[:, 1][m]
         counts = torch.bincount(rid, minlength=G_R)
         ev[1].record()
-        sums = torch.zeros(G_R, dtype=torch.int64, device="cuda").index_add_(0, rid, values[srid])
+        if torch_reduce:
+            sums = torch.zeros(G_R, dtype=acc, device="cuda").index_add_(0, rid, values[srid].to(acc))
         ev[2].record()
         torch.cuda.synchronize()
         if it >= a.warmup:
             torch_ms["count"].append(ev[0].elapsed_time(ev[1]))
             torch_ms["sum"].append(ev[1].elapsed_time(ev[2]))
-    assert torch.equal(counts, want_counts) and torch.equal(sums, want_sums)
+    assert torch.equal(counts, want_counts)
+    if torch_reduce:
+        assert torch.equal(sums, want_sums)
+    else:
+        sums = None
     # the same pair list reduced to [sum, min, max] of the three columns (configuration g's baseline)
     torch_agg_ms = []
-    for it in range(a.warmup + a.steps):
+    for it in range(a.warmup + a.steps if torch_reduce else 0):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         ev[0].record()
         m = pairs[:, 1] != hpcjoin.NULL_RID
         rid, srid = pairs[:, 0][m], pairs[:, 1][m]
         counts = torch.bincount(rid, minlength=G_R)
-        t_sum = torch.zeros(G_R, dtype=torch.int64, device="cuda").index_add_(0, rid, cols[0][srid])
-        t_min = torch.full((G_R,), 2**63 - 1, dtype=torch.int64, device="cuda").scatter_reduce_(
-            0, rid, cols[1][srid], "amin", include_self=True)
-        t_max = torch.full((G_R,), -2**63, dtype=torch.int64, device="cuda").scatter_reduce_(
-            0, rid, cols[2][srid], "amax", include_self=True)
+        t_sum = torch.zeros(G_R, dtype=acc, device="cuda").index_add_(0, rid, cols[0][srid].to(acc))
+        t_min = torch.full((G_R,), IDENT["min"], dtype=acc, device="cuda").scatter_reduce_(
+            0, rid, cols[1][srid].to(acc), "amin", include_self=True)
+        t_max = torch.full((G_R,), IDENT["max"], dtype=acc, device="cuda").scatter_reduce_(
+            0, rid, cols[2][srid].to(acc), "amax", include_self=True)
         ev[1].record()
         torch.cuda.synchronize()
         if it >= a.warmup:
             torch_agg_ms.append(ev[0].elapsed_time(ev[1]))
-    assert torch.equal(t_sum, want[(0, "sum")]) and torch.equal(t_min, want[(1, "min")]) and torch.equal(t_max, want[(2, "max")])
-    del t_sum, t_min, t_max
+    if torch_reduce:
+        assert torch.equal(t_sum, want[(0, "sum")]) and torch.equal(t_min, want[(1, "min")]) and torch.equal(t_max, want[(2, "max")])
+        del t_sum, t_min, t_max
     total = {k: [r["join_ms"] + t for r, t in zip(runs, torch_ms[k])] for k in ("count", "sum")}
     total["sum"] = [x + c for x, c in zip(total["sum"], torch_ms["count"])]  # the mask and rids are shared
     total["agg"] = [r["join_ms"] + t for r, t in zip(runs, torch_agg_ms)]
+
+    def timed(v):  # null where the torch reduction was not run
+        return _spread(v) if torch_reduce else None
     lines["a"] = report("a", "LEFT_OUTER materialize + torch bincount / index_add_", j, runs, {
-        "rows": int(pairs.shape[0]), "torch_count_ms": _spread(torch_ms["count"]), "torch_sum_ms": _spread(torch_ms["sum"]),
-        "total_count_ms": _spread(total["count"]), "total_sum_ms": _spread(total["sum"]),
-        "torch_sum_min_max_ms": _spread(torch_agg_ms), "total_sum_min_max_ms": _spread(total["agg"])})
+        "rows": int(pairs.shape[0]), "torch_count_ms": _spread(torch_ms["count"]), "torch_sum_ms": timed(torch_ms["sum"]),
+        "total_count_ms": _spread(total["count"]), "total_sum_ms": timed(total["sum"]),
+        "torch_sum_min_max_ms": timed(torch_agg_ms), "total_sum_min_max_ms": timed(total["agg"]),
+        "torch_reductions_timed": torch_reduce})
     del j, pairs, m, rid, srid, counts, sums
     ctx.trim_workspace()
     torch.cuda.empty_cache()
@@ -211,7 +262,7 @@ def main():
         if it >= a.warmup:
             runs.append(res)
     rows = rows.cuda()
-    assert rows.shape == (G_R, 3) and torch.equal(by_rid(rows, 1), want_counts) and torch.equal(by_rid(rows, 2), want_sums)
+    assert rows.shape == (G_R, 3) and torch.equal(by_rid(rows, 1), want_counts) and torch.equal(by_rid(rows, 2), bits(want_sums))
     lines["d"] = report("d", "GROUP materialize, counts and sums (join_group)", j, runs, {"rows": G_R})
 
     del rows, j
@@ -226,7 +277,7 @@ def main():
             res, rows = j.join_group(ctx, cols[c], 0, G_S)
             step.append(res)
             if it == a.warmup + a.steps - 1:
-                assert torch.equal(by_rid(rows.cuda(), 2), want[(c, "sum")])
+                assert torch.equal(by_rid(rows.cuda(), 2), bits(want[(c, "sum")]))
         if it >= a.warmup:
             merged = dict(step[-1])
             merged["join_ms"] = sum(r["join_ms"] for r in step)
@@ -250,7 +301,8 @@ def main():
         rows = rows.cuda()
         assert rows.shape == (G_R, 2 + len(columns)) and torch.equal(by_rid(rows, 1), want_counts)
         for k, w in enumerate(wanted):
-            assert torch.equal(by_rid(rows, 2 + k), want[w]), (name, k)
+            assert torch.equal(by_rid(rows, 2 + k), bits(want[w])), (name, k)
+        assert rr[-1]["group_dtypes"] == ["float64" if is_float else "int64"] * len(columns)
         lines[name] = report(name, what, jj, rr, {"rows": G_R, "columns": len(columns), "aggs": aggs})
         del rows, jj
         ctx.trim_workspace()
@@ -264,12 +316,13 @@ def main():
              [(0, "min"), (1, "sum"), (2, "max"), (0, "sum")])
     a_agg = lines["a"]["total_sum_min_max_ms"]
     print(json.dumps({
-        "workload": wl.name, "comparison": "aggregated columns, join_ms medians",
+        "workload": wl.name, "value_dtype": a.value_dtype, "comparison": "aggregated columns, join_ms medians",
         "e_three_join_group": lines["e"]["join_ms"]["median"], "f_sum_sum_sum": lines["f"]["join_ms"]["median"],
         "e_over_f": round(lines["e"]["join_ms"]["median"] / lines["f"]["join_ms"]["median"], 3),
         "e_over_f_build_probe": round(lines["e"]["dev_build_probe_ms"]["median"] / lines["f"]["dev_build_probe_ms"]["median"], 3),
         "a_sum_min_max": a_agg, "g_sum_min_max": lines["g"]["join_ms"]["median"],
-        "a_over_g": round(a_agg["median"] / lines["g"]["join_ms"]["median"], 3),
+        "a_over_g": round(a_agg["median"] / lines["g"]["join_ms"]["median"], 3) if a_agg else None,
+        "torch_reductions_timed": torch_reduce,
         "build_probe_ms_by_columns": {"join_group": lines["d"]["dev_build_probe_ms"]["median"],
                                       **{str(k): lines["h%d" % k]["dev_build_probe_ms"]["median"] for k in (1, 2, 3, 4)}},
         "checked": "counts, sums, minima and maxima equal the oracle"}), flush=True)
@@ -277,10 +330,11 @@ def main():
     a_count, a_sum = lines["a"]["total_count_ms"], lines["a"]["total_sum_ms"]
     c_med, d_med, b_med = (lines[k]["join_ms"]["median"] for k in ("c", "d", "b"))
     print(json.dumps({
-        "workload": wl.name, "comparison": "join_ms medians (a: join_ms + torch part)",
+        "workload": wl.name, "value_dtype": a.value_dtype, "comparison": "join_ms medians (a: join_ms + torch part)",
         "a_count": a_count, "a_sum": a_sum, "b": b_med, "c": c_med, "d": d_med,
         "c_below_a_beyond_spread": a_count["median"] - c_med > a_count["max"] - a_count["min"],
-        "d_below_a_beyond_spread": a_sum["median"] - d_med > a_sum["max"] - a_sum["min"],
+        "d_below_a_beyond_spread": (a_sum["median"] - d_med > a_sum["max"] - a_sum["min"]) if a_sum else None,
+        "torch_reductions_timed": torch_reduce,
         "c_over_b": round(c_med / b_med, 3),
         "c_over_b_build_probe": round(lines["c"]["dev_build_probe_ms"]["median"] / lines["b"]["dev_build_probe_ms"]["median"], 3),
         "checked": "counts and sums equal the oracle"}), flush=True)
