@@ -44,9 +44,9 @@ struct Case {
   core::JoinKind kind = core::JoinKind::Inner;
   // semi / anti on the set-semantics bitmap plan (JoinConfig::semiBitmap): one rank, the plan must be taken
   bool semiBitmap = false;
-  // kind Group: sum an outer value column per group (HashJoin::joinGroup; one rank), else counts only
+  // kind Group: sum an outer value column per group (HashJoin::joinGroup with one int64 SUM column; one rank), else counts only
   bool groupValues = false;
-  // kind Group: sum, min and max of three strided outer columns per group (HashJoin::joinGroupAgg; one rank)
+  // kind Group: sum, min and max of three strided outer columns per group (HashJoin::joinGroup; one rank)
   bool groupAgg = false;
   // kind Group: typed columns -- float64 sum, float32 min (stride 2), int32 max (stride 3) per group
   bool groupTyped = false;
@@ -114,6 +114,11 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
         for (uint64_t i = 0; i < GS; ++i) values[3 * i + 1] = groupValue(i);
       }
       kernels::GroupColumns cols;
+      if (c.groupValues) {
+        cols.n = 1;
+        cols.col[0] = values.data() + 1;
+        cols.stride[0] = 3;
+      }
       if (c.groupAgg) {  // words 0, 1, 2 of 3-word rows: sum of the first, min of the second, max of the third
         values.assign(3 * GS, 0);
         for (uint64_t i = 0; i < 3 * GS; ++i) values[i] = groupValue(i);
@@ -151,13 +156,11 @@ bool runCase(const Case &c, uint32_t ranks, uint64_t G) {
         cols.agg[1] = kernels::GROUP_MIN;
         cols.agg[2] = kernels::GROUP_MAX;
       }
-      operators::JoinResult res = c.groupAgg || c.groupTyped ? j.joinGroupAgg(cols, 0, GS)
-                                  : c.groupValues ? j.joinGroup(values.data() + 1, 0, GS, 3)
-                                                  : j.run();
+      operators::JoinResult res = cols.n ? j.joinGroup(cols, 0, GS, "joinGroup") : j.run();
       if (groupKind) {
         const uint64_t W = c.groupAgg || c.groupTyped ? 5 : c.groupValues ? 3 : 2;
         if (res.localMatches != res.outputGroups || res.unmatchedOuter != 0 || res.outputPairs != 0 ||
-            res.outputRids != 0 || res.groupSums != c.groupValues || res.groupColumns != W - 2 || !j.getOutputGroups())
+            res.outputRids != 0 || (res.groupColumns == 1) != c.groupValues || res.groupColumns != W - 2 || !j.getOutputGroups())
           throw std::runtime_error("group join: the result fields do not add up");
         groups[r].assign(j.getOutputGroups(), j.getOutputGroups() + res.outputGroups * W);
         uint64_t pairsSum = 0, zeros = 0;

@@ -680,134 +680,6 @@ py::dict opBuildProbeOuterRows(const at::Tensor &R, const at::Tensor &S, const a
   return buildProbeOuterImpl(R, S, partR, partS, fragShift, keyShift, wide, rChunk, sChunk, keepInner, keepOuter, &pr);
 }
 
-static bool groupDtypeOf(at::ScalarType t, uint32_t &code);
-static std::string groupTorchDtypeName(at::ScalarType t);
-py::dict opBuildProbeGroupAgg(const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR, const at::Tensor &partS,
-                              int64_t fragShift, int64_t keyShift, bool wide, int64_t rChunk, int64_t sChunk,
-                              const std::vector<at::Tensor> &columns, const std::vector<std::string> &aggs,
-                              int64_t ridOffset);
-
-// ---- group join over partition-major inputs: LDS counters / sums, inner units, rows ----
-// rows: int64 [|R|, 2] (inner rid, count) or, with values, [|R|, 3] (inner rid,
-// count, sum); counts / sums: the raw accumulators by position of R (int64;
-// sums all 0 without values) (kernels/group_join.hip and the host twins).
-py::dict opBuildProbeGroup(const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR, const at::Tensor &partS,
-                           int64_t fragShift, int64_t keyShift, bool wide, int64_t rChunk, int64_t sChunk,
-                           const c10::optional<at::Tensor> &values, int64_t ridOffset) {
-  TORCH_CHECK(R.device() == S.device(), "R and S must live on the same device");
-  TORCH_CHECK(rChunk >= 1 && sChunk >= 1, "r_chunk and s_chunk must be positive");
-  TORCH_CHECK((uint64_t)S.size(0) < (1ull << 32), "build_probe_group: the per-group counters are 32 bits wide");
-  setDevice(R);
-  const bool sum = values.has_value() && values->defined();
-  const unsigned long long *vals = nullptr;
-  uint64_t stride = 1;
-  if (sum && values->dim() == 1 && values->scalar_type() != at::kLong) {
-    // int32, float64 or float32 values: the aggregate path with one "sum" column ("sums": the int64 words of its
-    // accumulators, binary64 bits for the float types); every other dtype is refused here.
-    uint32_t code = 0;
-    TORCH_CHECK(groupDtypeOf(values->scalar_type(), code), "build_probe_group: values have dtype ",
-                groupTorchDtypeName(values->scalar_type()), "; a 1-D int64, int32, float64 or float32 tensor is needed");
-    py::dict d = opBuildProbeGroupAgg(R, S, partR, partS, fragShift, keyShift, wide, rChunk, sChunk, {*values}, {"sum"},
-                                      ridOffset);
-    d["sums"] = d["aggs"].cast<at::Tensor>().select(0, 0);
-    return d;
-  }
-  if (sum) {
-    const at::Tensor &v = *values;
-    TORCH_CHECK(v.dim() == 1 && v.scalar_type() == at::kLong && v.device() == R.device(),
-                "build_probe_group: values must be a 1-D int64 tensor on the device of R and S");
-    TORCH_CHECK(v.size(0) == 0 || v.stride(0) >= 1, "build_probe_group: values need a positive element stride");
-    vals = reinterpret_cast<const unsigned long long *>(v.data_ptr());
-    stride = v.size(0) ? (uint64_t)v.stride(0) : 1;
-    if (S.size(0)) {  // every outer rid must have a value
-      at::Tensor rid = wide ? S.select(1, 1) : at::bitwise_and(S.reshape({-1}), keyShift >= 64 ? -1 : ((int64_t(1) << keyShift) - 1));
-      const int64_t lo = rid.min().item<int64_t>(), hi = rid.max().item<int64_t>();
-      TORCH_CHECK(lo >= ridOffset && hi - ridOffset < v.size(0), "build_probe_group: values [", ridOffset, ", ",
-                  ridOffset + v.size(0), ") do not cover the outer rids [", lo, ", ", hi, "]");
-    }
-  }
-  kernels::BPArgs a;
-  a.R = R.data_ptr();
-  a.S = S.data_ptr();
-  at::Tensor pr = partR.to(R.device()).contiguous(), ps = partS.to(R.device()).contiguous();
-  TORCH_CHECK(pr.size(0) == ps.size(0) && pr.size(0) >= 1, "part_r and part_s must have the same P + 1 entries");
-  a.partR = ptr<uint64_t>(pr);
-  a.partS = ptr<uint64_t>(ps);
-  a.P = (uint32_t)pr.size(0) - 1;
-  a.rChunk = (uint32_t)rChunk;
-  a.sChunk = (uint32_t)sChunk;
-  a.fragShift = (uint32_t)fragShift;
-  a.keyShift = (uint32_t)keyShift;
-  a.wide = wide;
-  const int64_t nR = R.size(0), nS = S.size(0), W = sum ? 3 : 2;
-  at::Tensor accCount = at::zeros({nR + 2}, like(R, at::kInt)), accSum = at::zeros({nR + 2}, like(R));
-  at::Tensor rows = at::empty({nR, W}, like(R));
-  uint64_t matched = 0, zeros = 0;
-  if (R.is_cuda()) {
-    at::Tensor ctr = at::zeros({8}, like(R));
-    auto *c = reinterpret_cast<unsigned long long *>(ctr.data_ptr());
-    a.result = c;
-    uint32_t *nItems = reinterpret_cast<uint32_t *>(c + 2), *nUnits = reinterpret_cast<uint32_t *>(c + 6);
-    const int64_t P1 = std::max<int64_t>(a.P, 1);
-    at::Tensor counts = at::empty({P1}, like(R, at::kInt)), offsets = at::empty({P1}, like(R, at::kInt));
-    kernels::BPArgs ua = kernels::outerSwapSides(a, std::min<uint32_t>(a.rChunk, kernels::MARK_UNIT));
-    ua.result = c + 4;
-    const uint32_t unitCap = a.P + (uint32_t)(nR / ua.sChunk) + 1;
-    uint32_t capacity = 2 * a.P + (uint32_t)(nS / a.sChunk + nR / a.rChunk) + 1024;
-    at::Tensor items, scanWs;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-      items = at::empty({(int64_t)capacity * 2}, like(R));
-      scanWs = at::empty({(int64_t)kernels::scanWorkspaceBytes(std::max<uint64_t>(a.P, unitCap)) / 4 + 1},
-                         like(R, at::kInt));
-      ctr.zero_();
-      accCount.zero_();
-      accSum.zero_();
-      kernels::bpPlanCounts(a, ptr<uint32_t>(counts), nullptr);
-      kernels::scanExclusiveU32(ptr<uint32_t>(counts), ptr<uint32_t>(offsets), a.P, nItems, scanWs.data_ptr(), nullptr);
-      kernels::bpEmit(a, ptr<uint32_t>(counts), ptr<uint32_t>(offsets), ptr<kernels::BPItem>(items), capacity, nullptr);
-      kernels::bpGroup(a, ptr<kernels::BPItem>(items), nItems, capacity, vals, (uint64_t)ridOffset, stride,
-                       ptr<uint32_t>(accCount), sum ? ptr<unsigned long long>(accSum) : nullptr, nullptr);
-      HIP_CHECK(hipDeviceSynchronize());
-      const uint32_t need = (uint32_t)(ctr.cpu()[2].item<int64_t>() & 0xFFFFFFFF);
-      if (need <= capacity) break;
-      TORCH_CHECK(attempt == 0, "build_probe_group: the work-item list overflowed twice");
-      capacity = need;
-    }
-    at::Tensor units = at::empty({(int64_t)unitCap}, like(R)), unitCounts = at::zeros({(int64_t)unitCap}, like(R, at::kInt)),
-               unitOffsets = at::empty({(int64_t)unitCap}, like(R));
-    kernels::markPlanUnits(ua, ptr<uint32_t>(counts), nullptr);
-    kernels::scanExclusiveU32(ptr<uint32_t>(counts), ptr<uint32_t>(offsets), a.P, nUnits, scanWs.data_ptr(), nullptr);
-    kernels::markEmitUnits(ua, ptr<uint32_t>(counts), ptr<uint32_t>(offsets), ptr<kernels::MarkUnit>(units), unitCap,
-                           nullptr);
-    kernels::groupUnitLengths(ua, ptr<kernels::MarkUnit>(units), nUnits, unitCap, ptr<uint32_t>(unitCounts), nullptr);
-    kernels::scanExclusiveU32to64(ptr<uint32_t>(unitCounts), ptr<unsigned long long>(unitOffsets), unitCap, c + 1,
-                                  scanWs.data_ptr(), nullptr);
-    kernels::groupEmit(ua, ptr<kernels::MarkUnit>(units), nUnits, unitCap, ptr<uint32_t>(accCount),
-                       sum ? ptr<unsigned long long>(accSum) : nullptr, ptr<unsigned long long>(unitOffsets),
-                       ptr<unsigned long long>(rows), (uint64_t)nR, nullptr);
-    HIP_CHECK(hipDeviceSynchronize());
-    at::Tensor h = ctr.cpu();
-    matched = (uint64_t)h[0].item<int64_t>();
-    zeros = (uint64_t)h[4].item<int64_t>();
-    TORCH_CHECK(h[1].item<int64_t>() == nR, "build_probe_group: the partitions hold ", h[1].item<int64_t>(),
-                " inner tuples, R has ", nR);
-  } else {
-    uint64_t n = 0;
-    matched = host::buildProbeGroup(a, reinterpret_cast<const uint64_t *>(vals), (uint64_t)ridOffset, stride,
-                                    ptr<uint32_t>(accCount), ptr<uint64_t>(accSum));
-    zeros = host::groupEmit(a, ptr<uint32_t>(accCount), sum ? ptr<uint64_t>(accSum) : nullptr, ptr<uint64_t>(rows),
-                            (uint64_t)nR, &n);
-    TORCH_CHECK((int64_t)n == nR, "build_probe_group: the partitions hold ", n, " inner tuples, R has ", nR);
-  }
-  py::dict d;
-  d["rows"] = rows;
-  d["counts"] = accCount.narrow(0, 0, nR).to(at::kLong);
-  d["sums"] = accSum.narrow(0, 0, nR);
-  d["matched_pairs"] = matched;
-  d["unmatched_inner"] = zeros;
-  return d;
-}
-
 // The element types a group join aggregates (kernels::GroupDtype); false for any other torch dtype.
 static bool groupDtypeOf(at::ScalarType t, uint32_t &code) {
   switch (t) {
@@ -873,28 +745,31 @@ static kernels::GroupColumns groupColumnsOf(const char *who, const std::vector<a
   return c;
 }
 
-// ---- group join with aggregated value columns over partition-major inputs ----
+// ---- group join over partition-major inputs: LDS counters / aggregates, inner units, rows ----
+// The one implementation behind build_probe_group and build_probe_group_agg (`who`); no column: counts only.
 // rows: int64 [|R|, 2 + C] (inner rid, count, agg_0, ...); counts [|R|] and aggs [C, |R|]: the raw accumulators by
-// position of R (kernels::groupAggFill / bpGroupAgg / groupEmitAgg and the host twins).
-py::dict opBuildProbeGroupAgg(const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR, const at::Tensor &partS,
-                              int64_t fragShift, int64_t keyShift, bool wide, int64_t rChunk, int64_t sChunk,
-                              const std::vector<at::Tensor> &columns, const std::vector<std::string> &aggs,
-                              int64_t ridOffset) {
+// position of R (kernels::groupAggInit / bpGroup / groupEmit and the host twins).
+static py::dict buildProbeGroupImpl(const char *who, const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR,
+                                    const at::Tensor &partS, int64_t fragShift, int64_t keyShift, bool wide,
+                                    int64_t rChunk, int64_t sChunk, const std::vector<at::Tensor> &columns,
+                                    const std::vector<std::string> &aggs, int64_t ridOffset) {
   TORCH_CHECK(R.device() == S.device(), "R and S must live on the same device");
   TORCH_CHECK(rChunk >= 1 && sChunk >= 1, "r_chunk and s_chunk must be positive");
-  TORCH_CHECK((uint64_t)S.size(0) < (1ull << 32), "build_probe_group_agg: the per-group counters are 32 bits wide");
+  TORCH_CHECK((uint64_t)S.size(0) < (1ull << 32), who, ": the per-group counters are 32 bits wide");
   setDevice(R);
-  TORCH_CHECK(!columns.empty(), "build_probe_group_agg: needs at least one value column");
-  kernels::GroupColumns cols = groupColumnsOf("build_probe_group_agg", columns, aggs, R.is_cuda(), columns[0].size(0));
-  for (const at::Tensor &v : columns)
-    TORCH_CHECK(v.device() == R.device(), "build_probe_group_agg: the columns must be on the device of R and S");
-  cols.offset = (uint64_t)ridOffset;
-  cols.rows = (uint64_t)columns[0].size(0);
-  if (S.size(0)) {  // every outer rid must have a value
-    at::Tensor rid = wide ? S.select(1, 1) : at::bitwise_and(S.reshape({-1}), keyShift >= 64 ? -1 : ((int64_t(1) << keyShift) - 1));
-    const int64_t lo = rid.min().item<int64_t>(), hi = rid.max().item<int64_t>();
-    TORCH_CHECK(lo >= ridOffset && hi - ridOffset < (int64_t)cols.rows, "build_probe_group_agg: values [", ridOffset, ", ",
-                ridOffset + (int64_t)cols.rows, ") do not cover the outer rids [", lo, ", ", hi, "]");
+  kernels::GroupColumns cols;
+  if (!columns.empty()) {
+    cols = groupColumnsOf(who, columns, aggs, R.is_cuda(), columns[0].size(0));
+    for (const at::Tensor &v : columns)
+      TORCH_CHECK(v.device() == R.device(), who, ": the columns must be on the device of R and S");
+    cols.offset = (uint64_t)ridOffset;
+    cols.rows = (uint64_t)columns[0].size(0);
+    if (S.size(0)) {  // every outer rid must have a value
+      at::Tensor rid = wide ? S.select(1, 1) : at::bitwise_and(S.reshape({-1}), keyShift >= 64 ? -1 : ((int64_t(1) << keyShift) - 1));
+      const int64_t lo = rid.min().item<int64_t>(), hi = rid.max().item<int64_t>();
+      TORCH_CHECK(lo >= ridOffset && hi - ridOffset < (int64_t)cols.rows, who, ": values [", ridOffset, ", ",
+                  ridOffset + (int64_t)cols.rows, ") do not cover the outer rids [", lo, ", ", hi, "]");
+    }
   }
   kernels::BPArgs a;
   a.R = R.data_ptr();
@@ -931,16 +806,16 @@ py::dict opBuildProbeGroupAgg(const at::Tensor &R, const at::Tensor &S, const at
                          like(R, at::kInt));
       ctr.zero_();
       accCount.zero_();
-      kernels::groupAggFill(cols, ptr<unsigned long long>(accAgg), (uint64_t)slots, nullptr);
+      kernels::groupAggInit(cols, ptr<unsigned long long>(accAgg), (uint64_t)slots, nullptr);
       kernels::bpPlanCounts(a, ptr<uint32_t>(counts), nullptr);
       kernels::scanExclusiveU32(ptr<uint32_t>(counts), ptr<uint32_t>(offsets), a.P, nItems, scanWs.data_ptr(), nullptr);
       kernels::bpEmit(a, ptr<uint32_t>(counts), ptr<uint32_t>(offsets), ptr<kernels::BPItem>(items), capacity, nullptr);
-      kernels::bpGroupAgg(a, ptr<kernels::BPItem>(items), nItems, capacity, cols, ptr<uint32_t>(accCount),
-                          ptr<unsigned long long>(accAgg), (uint64_t)slots, nullptr);
+      kernels::bpGroup(a, ptr<kernels::BPItem>(items), nItems, capacity, cols, ptr<uint32_t>(accCount),
+                       ptr<unsigned long long>(accAgg), (uint64_t)slots, nullptr);
       HIP_CHECK(hipDeviceSynchronize());
       const uint32_t need = (uint32_t)(ctr.cpu()[2].item<int64_t>() & 0xFFFFFFFF);
       if (need <= capacity) break;
-      TORCH_CHECK(attempt == 0, "build_probe_group_agg: the work-item list overflowed twice");
+      TORCH_CHECK(attempt == 0, who, ": the work-item list overflowed twice");
       capacity = need;
     }
     at::Tensor units = at::empty({(int64_t)unitCap}, like(R)), unitCounts = at::zeros({(int64_t)unitCap}, like(R, at::kInt)),
@@ -952,21 +827,21 @@ py::dict opBuildProbeGroupAgg(const at::Tensor &R, const at::Tensor &S, const at
     kernels::groupUnitLengths(ua, ptr<kernels::MarkUnit>(units), nUnits, unitCap, ptr<uint32_t>(unitCounts), nullptr);
     kernels::scanExclusiveU32to64(ptr<uint32_t>(unitCounts), ptr<unsigned long long>(unitOffsets), unitCap, c + 1,
                                   scanWs.data_ptr(), nullptr);
-    kernels::groupEmitAgg(ua, ptr<kernels::MarkUnit>(units), nUnits, unitCap, ptr<uint32_t>(accCount),
-                          ptr<unsigned long long>(accAgg), (uint64_t)slots, cols.n, ptr<unsigned long long>(unitOffsets),
-                          ptr<unsigned long long>(rows), (uint64_t)nR, nullptr);
+    kernels::groupEmit(ua, ptr<kernels::MarkUnit>(units), nUnits, unitCap, ptr<uint32_t>(accCount),
+                       ptr<unsigned long long>(accAgg), (uint64_t)slots, cols.n, ptr<unsigned long long>(unitOffsets),
+                       ptr<unsigned long long>(rows), (uint64_t)nR, nullptr);
     HIP_CHECK(hipDeviceSynchronize());
     at::Tensor h = ctr.cpu();
     matched = (uint64_t)h[0].item<int64_t>();
     zeros = (uint64_t)h[4].item<int64_t>();
-    TORCH_CHECK(h[1].item<int64_t>() == nR, "build_probe_group_agg: the partitions hold ", h[1].item<int64_t>(),
-                " inner tuples, R has ", nR);
+    TORCH_CHECK(h[1].item<int64_t>() == nR, who, ": the partitions hold ", h[1].item<int64_t>(), " inner tuples, R has ",
+                nR);
   } else {
     uint64_t n = 0;
-    matched = host::buildProbeGroupAgg(a, cols, ptr<uint32_t>(accCount), ptr<uint64_t>(accAgg), (uint64_t)slots);
-    zeros = host::groupEmitAgg(a, ptr<uint32_t>(accCount), ptr<uint64_t>(accAgg), (uint64_t)slots, cols.n,
-                               ptr<uint64_t>(rows), (uint64_t)nR, &n);
-    TORCH_CHECK((int64_t)n == nR, "build_probe_group_agg: the partitions hold ", n, " inner tuples, R has ", nR);
+    matched = host::buildProbeGroup(a, cols, ptr<uint32_t>(accCount), ptr<uint64_t>(accAgg), (uint64_t)slots);
+    zeros = host::groupEmit(a, ptr<uint32_t>(accCount), ptr<uint64_t>(accAgg), (uint64_t)slots, cols.n,
+                            ptr<uint64_t>(rows), (uint64_t)nR, &n);
+    TORCH_CHECK((int64_t)n == nR, who, ": the partitions hold ", n, " inner tuples, R has ", nR);
   }
   py::dict d;
   d["rows"] = rows;
@@ -975,6 +850,29 @@ py::dict opBuildProbeGroupAgg(const at::Tensor &R, const at::Tensor &S, const at
   d["group_dtypes"] = groupWordDtypes(cols);
   d["matched_pairs"] = matched;
   d["unmatched_inner"] = zeros;
+  return d;
+}
+
+py::dict opBuildProbeGroupAgg(const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR, const at::Tensor &partS,
+                              int64_t fragShift, int64_t keyShift, bool wide, int64_t rChunk, int64_t sChunk,
+                              const std::vector<at::Tensor> &columns, const std::vector<std::string> &aggs,
+                              int64_t ridOffset) {
+  TORCH_CHECK(!columns.empty(), "build_probe_group_agg: needs at least one value column");
+  return buildProbeGroupImpl("build_probe_group_agg", R, S, partR, partS, fragShift, keyShift, wide, rChunk, sChunk,
+                             columns, aggs, ridOffset);
+}
+
+// values: a 1-D int64, int32, float64 or float32 tensor summed per group (rows [|R|, 3]), or none (rows [|R|, 2]).
+// sums: that column's accumulators by position of R (int64 words, binary64 bits for the float types; all 0 without
+// values).
+py::dict opBuildProbeGroup(const at::Tensor &R, const at::Tensor &S, const at::Tensor &partR, const at::Tensor &partS,
+                           int64_t fragShift, int64_t keyShift, bool wide, int64_t rChunk, int64_t sChunk,
+                           const c10::optional<at::Tensor> &values, int64_t ridOffset) {
+  std::vector<at::Tensor> columns;
+  if (values.has_value() && values->defined()) columns.push_back(*values);
+  py::dict d = buildProbeGroupImpl("build_probe_group", R, S, partR, partS, fragShift, keyShift, wide, rChunk, sChunk,
+                                   columns, std::vector<std::string>(columns.size(), "sum"), ridOffset);
+  d["sums"] = columns.empty() ? at::zeros({R.size(0)}, like(R)) : d["aggs"].cast<at::Tensor>().select(0, 0);
   return d;
 }
 
@@ -2384,8 +2282,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
             TORCH_CHECK(j.getConfig().kind == core::JoinKind::Group, "join_group needs kind=GROUP, this join has kind=",
                         core::joinKindName(j.getConfig().kind));
             TORCH_CHECK(j.getConfig().materialize, "join_group needs materialize=True");
-            // int32, float64 and float32 values (stride in elements of that dtype) take the aggregate path with one
-            // "sum" column: the sum word is int64 for int32 values, the bits of a binary64 for the float types.
+            // One "sum" column (stride in elements of its dtype): the sum word is int64 for int64 and int32 values,
+            // the bits of a binary64 for the float types.
             uint32_t code = kernels::GROUP_I64;
             TORCH_CHECK(outerValues.dim() == 1 && groupDtypeOf(outerValues.scalar_type(), code),
                         "join_group: outer_values must be a 1-D int64 tensor (or int32, float64, float32); column 0 has ",
@@ -2404,10 +2302,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
             operators::JoinResult r;
             {
               py::gil_scoped_release nogil;
-              if (code == kernels::GROUP_I64)
-                r = j.joinGroup(ptr<uint64_t>(outerValues), outerOffset, outerGlobal, cols.stride[0]);
-              else
-                r = j.joinGroupAgg(cols, outerOffset, outerGlobal);
+              r = j.joinGroup(cols, outerOffset, outerGlobal, "join_group");
             }
             py::dict d = resultToDict(r);
             d["group_dtypes"] = groupWordDtypes(cols);
@@ -2434,7 +2329,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
             operators::JoinResult r;
             {
               py::gil_scoped_release nogil;
-              r = j.joinGroupAgg(cols, outerOffset, outerGlobal);
+              r = j.joinGroup(cols, outerOffset, outerGlobal, "join_group_agg");
             }
             py::dict d = resultToDict(r);
             d["group_dtypes"] = groupWordDtypes(cols);  // "int64", or "float64": the word holds binary64 bits

@@ -121,7 +121,7 @@ JoinPlan makePlan(const JoinConfig &cfg, uint32_t numberOfNodes, uint64_t global
   // Group joins: final partitions of one LDS table (rChunk below), so that no
   // outer tuple is probed against several inner chunks.
   // Keys, u32 counters and groupColumns u64 accumulators per slot
-  // (kernels::bpGroup, bpGroupAgg).  Whether value columns come is known only
+  // (kernels::bpGroup).  Whether value columns come is known only
   // at run time, so the table is sized with them: the largest rChunk whose
   // table lets two workgroups share a CU (80 KiB each).  One column: 2048 (64
   // KiB + 64 B; wide 80 KiB + 64 B -> 1024, 40 KiB); two or three: 1024; four: 512.

@@ -83,10 +83,9 @@ enum class ExchangeMode : int {
 //   Group: the join followed by an aggregate grouped by the build side.  One
 //     row per inner tuple, also those without a partner: (inner rid, count)
 //     where count is the number of outer tuples with its key, or (inner rid,
-//     count, sum) with an outer value column (HashJoin::joinGroup; int64, the
-//     sum wraps), or (inner rid, count, agg_0, ..., agg_{C-1}) over C = 1 ...
-//     4 outer value columns, each with its own SUM, signed MIN or signed MAX
-//     (HashJoin::joinGroupAgg; JoinConfig::groupColumns sizes the LDS tables;
+//     count, agg_0, ..., agg_{C-1}) over C = 1 ... 4 outer value columns, each
+//     with its own SUM (wraps), signed MIN or signed MAX
+//     (HashJoin::joinGroup; JoinConfig::groupColumns sizes the LDS tables;
 //     an empty group carries each aggregate's identity: 0, INT64_MAX,
 //     INT64_MIN; AVG is sum / count on the caller's side).  Each column is
 //     int64, int32 (sign-extended, aggregated as int64), float64 or float32
@@ -145,7 +144,7 @@ struct JoinConfig {
   uint64_t buildTarget = 4096;  // target inner tuples per final partition (= one 256 x 16 LDS build batch)
   uint32_t rChunk = 0;          // max inner tuples per LDS table (0 = auto from LDS budget)
   uint32_t sChunk = 65536;      // max outer tuples per build/probe work item
-  // kind Group: the most value columns a run may aggregate (1 ... 4; HashJoin::joinGroupAgg).  The automatic
+  // kind Group: the most value columns a run may aggregate (1 ... 4; HashJoin::joinGroup).  The automatic
   // rChunk leaves room for this many 8-byte accumulators per LDS slot (8 bytes whatever the column's element type:
   // int64, int32, float64, float32); a run with more columns is refused.
   uint32_t groupColumns = 1;

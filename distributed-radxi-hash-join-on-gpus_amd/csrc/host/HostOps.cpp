@@ -456,83 +456,8 @@ BitmapSemiResult bitmapSemiRids(const uint32_t *r, const uint64_t *rBegin, const
   });
 }
 
-uint64_t buildProbeGroup(const kernels::BPArgs &a, const uint64_t *values, uint64_t ridOffset, uint64_t strideWords,
-                         uint32_t *accCount, uint64_t *accSum) {
-  uint64_t pairs = 0;
-  const uint64_t ridMask = a.keyShift >= 64 ? ~0ull : ((1ull << a.keyShift) - 1);
-  std::vector<uint64_t> bucket, next, rep;
-  auto key = [&](const void *base, uint64_t i) -> uint64_t {
-    if (a.wide) return static_cast<const data::Tuple *>(base)[i].key;
-    return a.keyShift >= 64 ? 0ull : static_cast<const uint64_t *>(base)[i] >> a.keyShift;
-  };
-  for (uint32_t p = 0; p < a.P; ++p) {
-    const uint64_t rb = a.partR[p], re = a.partREnd ? a.partREnd[p] : a.partR[p + 1], sb = a.partS[p],
-                   se = a.partSEnd ? a.partSEnd[p] : a.partS[p + 1];
-    const uint64_t nr = re - rb;
-    if (nr == 0 || se == sb) continue;  // one-sided partitions: every count stays 0
-    const uint64_t N = nextPow2(nr);
-    bucket.assign(N, 0);
-    next.assign(nr, 0);
-    rep.assign(nr, 0);  // the first inner tuple of each key aggregates for its copies
-    for (uint64_t t = 0; t < nr; ++t) {
-      const uint64_t k = key(a.R, rb + t), idx = kernels::mix64(k) & (N - 1);
-      rep[t] = t;
-      for (uint64_t hit = bucket[idx]; hit > 0; hit = next[hit - 1])
-        if (key(a.R, rb + hit - 1) == k) {
-          rep[t] = rep[hit - 1];
-          break;
-        }
-      next[t] = bucket[idx];
-      bucket[idx] = t + 1;
-    }
-    for (uint64_t s = sb; s < se; ++s) {
-      const uint64_t k = key(a.S, s);
-      for (uint64_t hit = bucket[kernels::mix64(k) & (N - 1)]; hit > 0; hit = next[hit - 1]) {
-        if (key(a.R, rb + hit - 1) != k) continue;
-        const uint64_t r = rb + rep[hit - 1];
-        ++accCount[r];
-        if (values) {
-          const uint64_t rid =
-              a.wide ? static_cast<const data::Tuple *>(a.S)[s].rid : (static_cast<const uint64_t *>(a.S)[s] & ridMask);
-          accSum[r] += values[(rid - ridOffset) * strideWords];
-        }
-        break;
-      }
-    }
-    for (uint64_t t = 0; t < nr; ++t) {  // copies take their key's totals; every tuple adds its count to the pairs
-      if (rep[t] != t) {
-        accCount[rb + t] = accCount[rb + rep[t]];
-        if (values) accSum[rb + t] = accSum[rb + rep[t]];
-      }
-      pairs += accCount[rb + t];
-    }
-  }
-  return pairs;
-}
-
-uint64_t groupEmit(const kernels::BPArgs &a, const uint32_t *accCount, const uint64_t *accSum, uint64_t *out,
-                   uint64_t outCapacity, uint64_t *rows) {
-  const uint64_t ridMask = a.keyShift >= 64 ? ~0ull : ((1ull << a.keyShift) - 1);
-  const uint64_t W = accSum ? 3 : 2;
-  uint64_t n = 0, zeros = 0;
-  for (uint32_t p = 0; p < a.P; ++p) {
-    const uint64_t b = a.partR[p], e = a.partREnd ? a.partREnd[p] : a.partR[p + 1];
-    for (uint64_t i = b; i < e; ++i) {
-      zeros += accCount[i] == 0;
-      if (out && n < outCapacity) {
-        out[n * W] = a.wide ? static_cast<const data::Tuple *>(a.R)[i].rid : (static_cast<const uint64_t *>(a.R)[i] & ridMask);
-        out[n * W + 1] = accCount[i];
-        if (accSum) out[n * W + 2] = accSum[i];
-      }
-      ++n;
-    }
-  }
-  if (rows) *rows = n;
-  return zeros;
-}
-
-uint64_t buildProbeGroupAgg(const kernels::BPArgs &a, const kernels::GroupColumns &cols, uint32_t *accCount,
-                            uint64_t *accAgg, uint64_t accSlots) {
+uint64_t buildProbeGroup(const kernels::BPArgs &a, const kernels::GroupColumns &cols, uint32_t *accCount,
+                         uint64_t *accAgg, uint64_t accSlots) {
   uint64_t pairs = 0;
   const uint64_t ridMask = a.keyShift >= 64 ? ~0ull : ((1ull << a.keyShift) - 1);
   for (uint32_t c = 0; c < cols.n; ++c)
@@ -615,8 +540,8 @@ uint64_t buildProbeGroupAgg(const kernels::BPArgs &a, const kernels::GroupColumn
   return pairs;
 }
 
-uint64_t groupEmitAgg(const kernels::BPArgs &a, const uint32_t *accCount, const uint64_t *accAgg, uint64_t accSlots,
-                      uint32_t columns, uint64_t *out, uint64_t outCapacity, uint64_t *rows) {
+uint64_t groupEmit(const kernels::BPArgs &a, const uint32_t *accCount, const uint64_t *accAgg, uint64_t accSlots,
+                   uint32_t columns, uint64_t *out, uint64_t outCapacity, uint64_t *rows) {
   const uint64_t ridMask = a.keyShift >= 64 ? ~0ull : ((1ull << a.keyShift) - 1);
   const uint64_t W = 2 + columns;
   uint64_t n = 0, zeros = 0;

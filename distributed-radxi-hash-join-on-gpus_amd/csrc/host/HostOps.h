@@ -89,29 +89,22 @@ BitmapSemiResult bitmapSemiCount(const uint32_t *r, const uint64_t *rBegin, cons
                                  uint32_t partitions, uint32_t bits);
 BitmapSemiResult bitmapSemiRids(const uint32_t *r, const uint64_t *rBegin, const uint64_t *s, const uint64_t *sBegin,
                                 uint32_t partitions, uint32_t keyShift, uint32_t bits, bool anti, uint64_t *out);
-// Group joins (twins of kernels/group_join.hip).  buildProbeGroup walks whole
-// partitions: accCount[r] (and, with values, accSum[r]) of every position r of
-// the partitioned inner buffer (zeroed by the caller) become the number of
-// outer tuples with r's key and the wrapping sum of values[(rid - ridOffset) *
-// strideWords] over them; returns the pairs (the sum of the counts).
-// groupEmit writes one row (rid, count[, sum]) per inner position of every
-// partition (accSum != null: three words; out may be null; rows at or beyond
-// outCapacity are counted, not stored), stores their number in *rows and
-// returns the groups with count 0.
-uint64_t buildProbeGroup(const kernels::BPArgs &a, const uint64_t *values, uint64_t ridOffset, uint64_t strideWords,
-                         uint32_t *accCount, uint64_t *accSum);
-uint64_t groupEmit(const kernels::BPArgs &a, const uint32_t *accCount, const uint64_t *accSum, uint64_t *out,
-                   uint64_t outCapacity, uint64_t *rows);
-// The same with cols.n aggregated value columns (twins of kernels::bpGroupAgg /
-// groupEmitAgg): accAgg is column-major, accAgg[c * accSlots + r], and is set
-// here to every column's identity first (accCount is zeroed by the caller).
-// Rows are (rid, count, agg_0, ..., agg_{columns-1}).  Typed columns
-// (cols.dtype) are widened as the kernel does -- int32 sign-extended, float32 to
-// binary64 -- and float columns aggregate as binary64 in sequential order.
-uint64_t buildProbeGroupAgg(const kernels::BPArgs &a, const kernels::GroupColumns &cols, uint32_t *accCount,
-                            uint64_t *accAgg, uint64_t accSlots);
-uint64_t groupEmitAgg(const kernels::BPArgs &a, const uint32_t *accCount, const uint64_t *accAgg, uint64_t accSlots,
-                      uint32_t columns, uint64_t *out, uint64_t outCapacity, uint64_t *rows);
+// Group joins (twins of kernels::bpGroup / groupEmit).  buildProbeGroup walks
+// whole partitions: accCount[r] of every position r of the partitioned inner
+// buffer (zeroed by the caller) becomes the number of outer tuples with r's
+// key, and accAgg[c * accSlots + r] (column-major; set here to every column's
+// identity first; untouched when cols.n == 0) the aggregate of column c over
+// them; returns the pairs (the sum of the counts).  Typed columns (cols.dtype)
+// are widened as the kernel does -- int32 sign-extended, float32 to binary64 --
+// and float columns aggregate as binary64 in sequential order.
+// groupEmit writes one row (rid, count, agg_0, ..., agg_{columns-1}) per inner
+// position of every partition (out may be null; rows at or beyond outCapacity
+// are counted, not stored), stores their number in *rows and returns the
+// groups with count 0.
+uint64_t buildProbeGroup(const kernels::BPArgs &a, const kernels::GroupColumns &cols, uint32_t *accCount,
+                         uint64_t *accAgg, uint64_t accSlots);
+uint64_t groupEmit(const kernels::BPArgs &a, const uint32_t *accCount, const uint64_t *accAgg, uint64_t accSlots,
+                   uint32_t columns, uint64_t *out, uint64_t outCapacity, uint64_t *rows);
 
 // Wire codec (kernels.h, WireCodec) over host segment lists.
 void wirePack(const uint64_t *raw, uint64_t *wire, const kernels::WireSeg *segs, uint32_t nSegs,

@@ -1,103 +1,86 @@
 // Group joins (core::JoinKind::Group): per inner tuple r the number of outer
-// tuples with r's key, and optionally the int64 sum (two's complement, wraps)
-// of one outer value column over those tuples -- the join followed by COUNT /
-// SUM ... GROUP BY the build side, without ever forming a pair.  With
-// aggregated value columns (GroupColumns): C = 1 ... 4 outer columns, each with
-// its own base pointer, stride and aggregate -- SUM (wraps), signed MIN or
-// signed MAX -- and rows (rid, count, agg_0, ..., agg_{C-1}).  A column may
-// also be int32 (accumulated as int64), float64 or float32 (accumulated as
-// binary64, the row word holding its bits): the TYPED kernels below.  AVG is
-// sum / count on the caller's side and is not built.
+// tuples with r's key and the aggregates of C = 0 ... 4 outer value columns
+// over those tuples -- the join followed by COUNT / SUM / MIN / MAX ... GROUP BY
+// the build side, without ever forming a pair.  The columns are one
+// GroupColumns (kernels.h: base pointer, element stride, aggregate and element
+// type per column; n = 0 counts only) and the rows are (rid, count, agg_0, ...,
+// agg_{C-1}), 2 + C words.  AVG is sum / count on the caller's side.
 //
-//  * bpGroupKernel<LAYOUT, DIRECT, SUM> -- persistent grid over the BPItem
-//    list, geometry of bpOuterCountKernel (256 threads, 16 tuples per thread
-//    and batch, the first inner and outer batch in flight while the table is
-//    cleared).  Hashed table: the key slots of the outer-join count, every
-//    inner copy in a slot of its own, next to one u32 counter per slot and
-//    with SUM one u64 accumulator per slot; only the *first* slot of a key
-//    aggregates.  An outer tuple stops at the first slot holding its key and
-//    does one LDS atomic add (with SUM a second, 64-bit one): it never walks
-//    the chain of copies.  The value is values[(rid - ridOffset) * stride],
-//    loaded non-temporally; the rids come in with the keys (one 8-byte load
-//    per compressed tuple instead of its high dword; wide tuples read the rid
-//    word of a tuple that found a slot), and the gathers of a
-//    thread's 16 tuples (wide tuples: 8) are all issued before the first one is consumed.  A
-//    tuple that found no slot forms no address.  After a barrier every inner
-//    tuple (still in registers when the item has one batch) looks up the first
-//    slot of its own key and adds that slot's count and sum to the global
-//    accumulators at its position rb + idx of the partitioned inner buffer:
-//    consecutive lanes hold consecutive positions.  An inner chunk is shared
-//    by all outer chunks of its partition, so the add is a global atomic,
-//    skipped when the item counted nothing for the tuple.  (A plain store for
-//    partitions of a single outer chunk was not built: it needs a second code
-//    path per item and nothing has measured the atomics as the bottleneck.)
-//    The item's pair total is the sum of the counts its inner tuples read;
-//    *a.result gets one 64-bit atomic per workgroup.
-//  * DIRECT (4-byte fragments of at most 13 bits, count only): table[fragment]
-//    is the number of outer tuples of the fragment.  No build: the probe adds
-//    one per outer tuple, the inner tuples read their fragment's counter.
-//    DIRECT is not built for SUM: the accumulators would be 12 B per fragment
-//    (96 KiB + 64 B at 13 bits, one workgroup per CU) and an outer tuple
-//    without a partner would still gather its value; SUM always takes the
-//    hashed table, whose size follows rChunk.  bpGroup() chooses accordingly.
-//  * groupUnitLengths / groupEmitKernel<LAYOUT, SUM> -- one wave per unit of
-//    the inner side (markPlanUnits / markEmitUnits over outerSwapSides(a,
-//    unit), also for partitions without outer tuples, which got no work item).
-//    Every valid position is selected, so a unit's row count is its length and
-//    the row offsets come from the u32-to-u64 scan.  Per position the row
-//    (rid, count[, sum]) is written; the wave's stores are consecutive 8-byte
-//    words of the unit's run (the three columns are interleaved through lane
-//    shuffles).  Zero counts are added to *a.result; without `out` the kernel
-//    only counts them.  Positions outside [partS, partSEnd) -- the gaps of a
-//    sampled local pass -- are never read.
-//  * bpGroupAggKernel<LAYOUT, C> -- bpGroupKernel<LAYOUT, hashed, SUM> with C
-//    8-byte accumulators per slot (column-major in LDS) and the columns passed
-//    by value (C pointers, strides and aggregate codes; the code is
-//    wave-uniform and branched on at run time: the kernel is templated on C
-//    only).  The table clear writes each accumulator's identity (0, INT64_MAX,
-//    INT64_MIN), not zeros.  The probe does the u32 add and one 64-bit LDS
-//    atomic per column: add, signed min or signed max.  The gathers of G
-//    tuples (C * G values) are issued before the first is consumed; G shrinks
-//    with C (16, 8, 4, 4; wide tuples 8, 4, 2, 2) so that nothing spills.  The
-//    inner side applies count and aggregates to global accumulators kept
-//    column-major, acc[c * accSlots + position]: 64-bit atomic add, signed min,
-//    signed max.  These must hold the identities before the launch:
-//    groupAggFillKernel writes them before every run (a memset cannot).
-//    The 64-bit atomics are native on gfx950 -- the assembly of this file holds
-//    ds_add_u64 / ds_min_i64 / ds_max_i64 and global_atomic_add_x2 / smin_x2 /
-//    smax_x2 and no compare-and-swap loop for them (read once, hipcc of ROCm
-//    7; the only ds_cmpst is the slot claim of the build).
-//    No direct-addressed variant, for the reasons given for SUM above.  One
-//    int64 column with SUM runs bpGroupKernel itself (bpGroupAgg() routes it).
-//  * bpGroupAggKernel<LAYOUT, C, TYPED> -- TYPED = false is the kernel above,
-//    for joins whose columns are all int64.  TYPED = true (any column int32,
-//    float64 or float32; one such column with SUM too): the element type is a
-//    kernel argument per column like the aggregate code, wave-uniform and
-//    branched on in scalar code.  The gather is a 4- or 8-byte non-temporal
-//    load of element row * stride (strides count elements of the column's own
-//    type) into a dword pair kept as loaded, so all C * G gathers are still
-//    issued before the first wait; the widening happens at the atomic: int32
-//    sign-extended, float32 converted to binary64 (v_cvt_f64_f32, exact).
-//    Accumulators stay 8 bytes per column and slot, so the LDS layout, the
-//    planned rChunk and G are those of TYPED = false.  Integer columns take
-//    the integer atomics above; float columns hold binary64 bits and take
-//    ds_add_f64 / ds_min_f64 / ds_max_f64 in LDS and global_atomic_add_f64 /
-//    min_f64 / max_f64 on the global accumulators (__hip_atomic_fetch_add /
-//    _min / _max on double, relaxed, workgroup and agent scope; read once in
-//    the assembly of this file: native, no compare-and-swap loop, no
-//    -munsafe-fp-atomics).  The hardware float atomics are valid on
-//    coarse-grained memory only: the global accumulators live in the engine's
-//    Arena or a torch tensor (hipMalloc) and must stay there.  Identities:
-//    +0.0, +inf, -inf (bits; groupAggIdentity).  A float SUM is the sum in the
-//    order the atomics land; MIN / MAX compare as IEEE numbers; NaN inputs and
-//    the order of -0.0 / +0.0 are unspecified.
-//  * groupEmitAggKernel<LAYOUT, C> -- groupEmitKernel<LAYOUT, SUM> with W = 2 +
-//    C words per row (4 to 6; one column takes groupEmitKernel's three): word q
-//    of the wave's run is stored by lane q % 64, so the stores stay consecutive
-//    8-byte words although W is no power of two.  Empty groups carry the
-//    identities the fill wrote.  Both emit kernels only move 8-byte words
-//    (loads, lane shuffles, stores; no arithmetic on an aggregate), so the
-//    bits of a float column pass through unchanged.
+// Build/probe.  Both kernels are a persistent grid over the BPItem list with
+// the geometry of bpOuterCountKernel: 256 threads, 16 tuples per thread and
+// batch, the first inner and outer batch in flight while the table is cleared.
+// Their phases are the same; groupHash, groupLoad, groupRid, groupInnerSlot and
+// groupAggAtomic are shared, the batch dispatch, the build loop and the slot
+// search are written out in both (why: profiles/group_unify/README.md).
+//  * table: the key slots of the outer-join count, every inner copy in a slot
+//    of its own (the only ds_cmpst of this file), next to one u32 counter and C
+//    u64 accumulators per slot (column-major in LDS); only the *first* slot of
+//    a key aggregates.  The clear writes each accumulator's identity.
+//  * probe: an outer tuple stops at the first slot holding its key and does one
+//    u32 LDS atomic and one 64-bit LDS atomic per column: it never walks the
+//    chain of copies.  The rids come in with the keys (one 8-byte load per
+//    compressed tuple instead of its high dword); wide tuples read the rid
+//    word only of a tuple that found a slot (16 preloaded 8-byte rids next to
+//    16 8-byte keys of either side spilled to scratch).  Column c's value is
+//    element (rid - offset) * stride[c], loaded non-temporally; the C * G
+//    gathers of G tuples are all issued before the first one is consumed, and
+//    a tuple that found no slot forms no address.
+//  * inner side: after a barrier every inner tuple (still in registers when the
+//    item has one batch) looks up the first slot of its own key and applies
+//    that slot's count and aggregates to the global accumulators at its
+//    position rb + idx of the partitioned inner buffer, accAgg[c * accSlots +
+//    position]: consecutive lanes hold consecutive positions.  An inner chunk
+//    is shared by all outer chunks of its partition, so these are global
+//    atomics, skipped when the item counted nothing for the tuple.  (A plain
+//    store for partitions of a single outer chunk was not built: it needs a
+//    second code path per item and nothing has measured the atomics as the
+//    bottleneck.)  The item's pair total is the sum of the counts its inner
+//    tuples read; *a.result gets one 64-bit atomic per workgroup.
+// bpGroup() alone decides which kernel runs:
+//  * bpGroupKernel<LAYOUT, DIRECT, SUM> -- no column, or one int64 column with
+//    SUM: no run-time branch on an aggregate or a type, G = 16 (wide tuples with
+//    SUM: 8).  DIRECT (4-byte fragments of at most 13 bits, count only):
+//    table[fragment] is the number of outer tuples of the fragment; no build,
+//    the probe adds one per outer tuple, the inner tuples read their fragment's
+//    counter.  DIRECT is not built with columns: the accumulators would be 12 B
+//    per fragment (96 KiB + 64 B at 13 bits, one workgroup per CU) and an outer
+//    tuple without a partner would still gather its value.
+//  * bpGroupAggKernel<LAYOUT, C, TYPED> -- everything else.  The aggregate code
+//    (and with TYPED the element type) of each column is a kernel argument,
+//    wave-uniform and branched on in scalar code.  G shrinks with C (16, 8, 4,
+//    4; wide tuples 8, 4, 2, 2) so that nothing spills.  TYPED = false: every
+//    column is int64.  TYPED = true (any column int32, float64 or float32): the
+//    gather is a 4- or 8-byte load into a dword pair kept as loaded, so the
+//    gathers are still issued before the first wait; the widening happens at
+//    the atomic: int32 sign-extended, float32 converted to binary64
+//    (v_cvt_f64_f32, exact).  Accumulators stay 8 bytes per column and slot, so
+//    the LDS layout, the planned rChunk and G do not depend on TYPED.
+// Arithmetic: integer columns accumulate as int64 (SUM wraps, MIN / MAX signed);
+// float columns hold binary64 bits -- SUM in the order the atomics land, MIN /
+// MAX as IEEE numbers, NaN inputs and the order of -0.0 / +0.0 unspecified.
+// Identities (groupAggIdentity): 0, INT64_MAX, INT64_MIN; +0.0, +inf, -inf.
+// The global accumulators must hold them before the launch: groupAggInit (a
+// zeroWords clear when every column is a SUM, groupAggFillKernel otherwise).
+// All 64-bit atomics are native on gfx950 -- ds_add_u64 / ds_min_i64 / ds_max_i64 /
+// ds_add_f64 / ds_min_f64 / ds_max_f64 and global_atomic_add_x2 / smin_x2 /
+// smax_x2 / add_f64 / min_f64 / max_f64, no compare-and-swap loop and no
+// -munsafe-fp-atomics (read once in the assembly, hipcc of ROCm 7).  The
+// hardware float atomics are valid on coarse-grained memory only: the global
+// accumulators live in the engine's Arena or a torch tensor (hipMalloc) and
+// must stay there.
+//
+// Rows.  groupUnitLengths / groupEmitKernel<LAYOUT, C> -- one wave per unit of
+// the inner side (markPlanUnits / markEmitUnits over outerSwapSides(a, unit),
+// also for partitions without outer tuples, which got no work item).  Every
+// valid position is selected, so a unit's row count is its length and the row
+// offsets come from the u32-to-u64 scan.  C = 0 stores one 16-byte row per
+// lane; C >= 1 stores word q of the wave's run from lane q % 64, the columns
+// interleaved through lane shuffles, so the stores stay consecutive 8-byte
+// words although W = 2 + C is no power of two.  The kernel only moves 8-byte
+// words: the bits of a float column pass through unchanged, and empty groups
+// carry the identities.  Zero counts are added to *a.result; without `out` the
+// kernel only counts them.  Positions outside [partS, partSEnd) -- the gaps of
+// a sampled local pass -- are never read.
 //
 // Count accumulators are u32: the caller refuses a global outer size of 2^32
 // or more (HashJoin, ops.build_probe_group).
@@ -106,32 +89,27 @@
 // tuples.  Key-only words are refused (no rid to report).
 //
 // Resources (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage; no
-// kernel uses scratch):
+// kernel uses scratch; per kernel in profiles/group_unify/README.md):
 //   bpGroupKernel<compressed>        121 VGPRs hashed, 120 direct; 3 workgroups per CU
 //   bpGroupKernel<split>             108 VGPRs hashed and direct; 4 workgroups per CU
 //   bpGroupKernel<wide>              176 VGPRs; 2 workgroups per CU
 //   bpGroupKernel<compressed, SUM>   234 VGPRs; 2 workgroups per CU
 //   bpGroupKernel<split, SUM>        186 VGPRs; 2 workgroups per CU
 //   bpGroupKernel<wide, SUM>         192 VGPRs; 2 workgroups per CU
-//   groupEmitKernel                  28-30 VGPRs (rid, count), 52-54 (rid, count, sum); 32 B LDS
-//   groupUnitLengthsKernel           12 VGPRs, no LDS
 //   bpGroupAggKernel<compressed, C>  238 / 240 / 234 / 248 VGPRs for C = 1 / 2 / 3 / 4; 2 workgroups per CU
 //   bpGroupAggKernel<split, C>       186 / 188 / 182 / 196 VGPRs; 2 workgroups per CU
 //   bpGroupAggKernel<wide, C>        212 / 206 / 200 / 206 VGPRs; 2 workgroups per CU
 //   bpGroupAggKernel<*, C, TYPED>    the VGPRs of TYPED = false (split, C = 3: 183) and 5 - 17 more SGPRs (at most
-//                                    106); 2 workgroups per CU, G unchanged (16, 8, 4, 4; wide 8, 4, 2, 2).  The
-//                                    C = 4 instantiations keep 12 (compressed), 15 (split) and 13 (wide) SGPRs in
-//                                    VGPR lanes, split C = 3 keeps 2 (SGPR spills inside the VGPR counts above:
-//                                    no scratch, no VGPR spill)
-//   groupEmitAggKernel<*, C>         62-64 / 73-76 / 86-87 VGPRs for C = 2 / 3 / 4; 32 B LDS
+//                                    106).  The C = 4 instantiations keep 12 (compressed), 15 (split) and 13 (wide)
+//                                    SGPRs in VGPR lanes, split C = 3 keeps 2 (SGPR spills inside the VGPR counts
+//                                    above: no scratch, no VGPR spill)
+//   groupEmitKernel<*, C>            28-30 / 52-54 / 62-64 / 73-76 / 86-87 VGPRs for C = 0 ... 4; 32 B LDS
+//   groupUnitLengthsKernel           12 VGPRs, no LDS
 //   groupAggFillKernel               10 VGPRs, no LDS
-//   LDS of bpGroupKernel (dynamic, bpGroupLdsBytes): hashed 4-byte keys + counters 32 KiB + 64 B at the
-//   planned rChunk 2048 (4096 slots), with sums 64 KiB + 64 B; 8-byte keys at the planned rChunk 1024 (2048
-//   slots) 24 KiB + 64 B, with sums 40 KiB + 64 B; direct 4 B << fragBits + 64 B (32 KiB + 64 B at 13 bits).
-//   A request above 160 KiB (a configured rChunk of 8192 with sums) is refused by bpGroup.
-//   LDS of bpGroupAggKernel: slots * (key + 4 + 8 C) + 64 B -- 4-byte keys at the planned rChunk 2048 / 1024 /
-//   1024 / 512 for C = 1 / 2 / 3 / 4: 64 / 48 / 64 / 40 KiB + 64 B; 8-byte keys at 1024 / 1024 / 1024 / 512: 40 /
-//   56 / 72 / 44 KiB + 64 B (two workgroups per CU each); above 160 KiB refused by bpGroupAgg.
+//   LDS (dynamic, bpGroupLdsBytes): slots * (key + 4 + 8 C) + 64 B, slots = groupMaxSlots(rChunk).  4-byte keys at
+//   the planned rChunk 2048 / 2048 / 1024 / 1024 / 512 for C = 0 ... 4: 32 / 64 / 48 / 64 / 40 KiB + 64 B; 8-byte
+//   keys at 1024 / 1024 / 1024 / 1024 / 512: 24 / 40 / 56 / 72 / 44 KiB + 64 B; direct 4 B << fragBits + 64 B (32
+//   KiB + 64 B at 13 bits).  A request above 160 KiB is refused by bpGroup.
 #include "kernels.h"
 #include "device_common.h"
 #include "mark_units.h"
@@ -144,6 +122,7 @@ namespace kernels {
 
 constexpr int GJ_T = 256;
 constexpr int GJ_K = 16;  // tuples per thread per batch (as the counting build/probe)
+constexpr uint32_t GJ_BATCH = GJ_T * GJ_K;
 constexpr uint32_t GJ_EMPTY32 = 0xFFFFFFFFu;
 constexpr unsigned long long GJ_EMPTY64 = ~0ull;
 constexpr uint32_t GJ_NONE = 0xFFFFFFFFu;  // probe: no slot holds the key
@@ -152,8 +131,9 @@ constexpr uint32_t GJ_DIRECT_MAX_BITS = 13;
 template <int LAYOUT>
 struct GroupKey {
   using type = typename std::conditional<LAYOUT == MK_WIDE, unsigned long long, uint32_t>::type;
+  static constexpr type EMPTY = LAYOUT == MK_WIDE ? (type)GJ_EMPTY64 : (type)GJ_EMPTY32;
 };
-// Rid registers of the outer side (SUM): the whole CompressedTuple, the u32 rid column, the Tuple's rid.
+// Rid registers of the outer side: the whole CompressedTuple, the u32 rid column, the Tuple's rid.
 template <int LAYOUT>
 struct GroupRid {
   using type = typename std::conditional<LAYOUT == MK_SPLIT, uint32_t, unsigned long long>::type;
@@ -167,6 +147,7 @@ __device__ __forceinline__ uint32_t groupHash(K key, uint32_t tbits) {
     return ((uint32_t)key * 2654435761u) >> (32 - tbits);
 }
 
+// ------------------------------------------------- phases of the build/probe
 // One batch of an item's keys into registers; RIDS: the rids as well.
 template <int LAYOUT, bool FULL, bool RIDS, typename K, typename R, int NR>
 __device__ __forceinline__ void groupLoad(const void *__restrict__ src, const uint16_t *__restrict__ hi, uint64_t off,
@@ -193,9 +174,26 @@ __device__ __forceinline__ void groupLoad(const void *__restrict__ src, const ui
     }
   }
 }
+// The rid in a register groupLoad<.., RIDS> filled.
+template <int LAYOUT, typename R>
+__device__ __forceinline__ uint64_t groupRid(R r, uint64_t ridMask) {
+  return LAYOUT == MK_COMPRESSED ? ((uint64_t)r & ridMask) : (uint64_t)r;
+}
 
-static bool groupDirect(const BPArgs &a, bool sum) {
-  return !sum && !a.wide && a.fragBits > 0 && a.fragBits <= GJ_DIRECT_MAX_BITS;
+// Inner side: the first slot of the key (it is in the table: this tuple inserted it).
+template <int LAYOUT, bool DIRECT, typename K>
+__device__ __forceinline__ uint32_t groupInnerSlot(const K *table, K key, uint32_t tbits, uint32_t mask) {
+  if constexpr (DIRECT) {
+    return (uint32_t)key & mask;
+  } else {
+    uint32_t h = groupHash<LAYOUT>(key, tbits);
+    while (table[h] != key) h = (h + 1) & mask;
+    return h;
+  }
+}
+
+static bool groupDirect(const BPArgs &a, bool columns) {
+  return !columns && !a.wide && a.fragBits > 0 && a.fragBits <= GJ_DIRECT_MAX_BITS;
 }
 
 // (HIP launch bounds: the second value is workgroups per CU, as bpOuterCountKernel; SUM holds the rids and 16
@@ -208,10 +206,8 @@ __global__ __launch_bounds__(GJ_T, LAYOUT == MK_WIDE || SUM ? 2 : LAYOUT == MK_S
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   using K = typename GroupKey<LAYOUT>::type;
   using R = typename GroupRid<LAYOUT>::type;
-  constexpr K EMPTY = LAYOUT == MK_WIDE ? (K)GJ_EMPTY64 : (K)GJ_EMPTY32;
-  constexpr uint32_t BATCH = GJ_T * GJ_K;
-  // The outer rids come in with the keys; wide tuples read theirs when a slot was found (see the probe).
-  constexpr bool PRE_RID = SUM && LAYOUT != MK_WIDE;
+  constexpr K EMPTY = GroupKey<LAYOUT>::EMPTY;
+  constexpr bool PRE_RID = SUM && LAYOUT != MK_WIDE;  // wide tuples read their rid when a slot was found
   static_assert(!DIRECT || (LAYOUT != MK_WIDE && !SUM), "direct-addressed tables count 4-byte fragments");
   const uint64_t maxSlots = DIRECT ? (uint64_t(1) << a.fragBits) : groupMaxSlots(a.rChunk);
   // [sum u64 x slots][key x slots][count u32 x slots][8 x u64 reduction words]; DIRECT: [count u32 x slots][...]
@@ -239,15 +235,10 @@ __global__ __launch_bounds__(GJ_T, LAYOUT == MK_WIDE || SUM ? 2 : LAYOUT == MK_S
     // First inner batch and first outer batch are in flight while the table is cleared.
     K rv[GJ_K], sv[GJ_K];
     R rr[PRE_RID ? GJ_K : 1], nor[1];
-    if (nr >= BATCH) groupLoad<LAYOUT, true, false>(a.R, a.Rhi, rb, nr, 0, a.fragShift, rv, nor);
+    if (nr >= GJ_BATCH) groupLoad<LAYOUT, true, false>(a.R, a.Rhi, rb, nr, 0, a.fragShift, rv, nor);
     else groupLoad<LAYOUT, false, false>(a.R, a.Rhi, rb, nr, 0, a.fragShift, rv, nor);
-    if constexpr (PRE_RID) {
-      if (ns >= BATCH) groupLoad<LAYOUT, true, true>(a.S, a.Shi, sb, ns, 0, a.fragShift, sv, rr);
-      else groupLoad<LAYOUT, false, true>(a.S, a.Shi, sb, ns, 0, a.fragShift, sv, rr);
-    } else {
-      if (ns >= BATCH) groupLoad<LAYOUT, true, false>(a.S, a.Shi, sb, ns, 0, a.fragShift, sv, rr);
-      else groupLoad<LAYOUT, false, false>(a.S, a.Shi, sb, ns, 0, a.fragShift, sv, rr);
-    }
+    if (ns >= GJ_BATCH) groupLoad<LAYOUT, true, PRE_RID>(a.S, a.Shi, sb, ns, 0, a.fragShift, sv, rr);
+    else groupLoad<LAYOUT, false, PRE_RID>(a.S, a.Shi, sb, ns, 0, a.fragShift, sv, rr);
     for (uint32_t i = t; i < slots; i += GJ_T) {
       cnt[i] = 0;
       if constexpr (!DIRECT) table[i] = EMPTY;
@@ -257,7 +248,7 @@ __global__ __launch_bounds__(GJ_T, LAYOUT == MK_WIDE || SUM ? 2 : LAYOUT == MK_S
 
     // ---- build: every inner copy takes a slot (DIRECT: nothing to build)
     if constexpr (!DIRECT) {
-      for (uint32_t b0 = 0; b0 < nr; b0 += BATCH) {
+      for (uint32_t b0 = 0; b0 < nr; b0 += GJ_BATCH) {
         if (b0) groupLoad<LAYOUT, false, false>(a.R, a.Rhi, rb, nr, b0, a.fragShift, rv, nor);
 #pragma unroll
         for (int k = 0; k < GJ_K; ++k) {
@@ -272,15 +263,10 @@ __global__ __launch_bounds__(GJ_T, LAYOUT == MK_WIDE || SUM ? 2 : LAYOUT == MK_S
     }
 
     // ---- probe: the first slot of the key, one LDS atomic (SUM: two)
-    for (uint32_t b0 = 0; b0 < ns; b0 += BATCH) {
+    for (uint32_t b0 = 0; b0 < ns; b0 += GJ_BATCH) {
       if (b0) {
-        if constexpr (PRE_RID) {
-          if (b0 + BATCH <= ns) groupLoad<LAYOUT, true, true>(a.S, a.Shi, sb, ns, b0, a.fragShift, sv, rr);
-          else groupLoad<LAYOUT, false, true>(a.S, a.Shi, sb, ns, b0, a.fragShift, sv, rr);
-        } else {
-          if (b0 + BATCH <= ns) groupLoad<LAYOUT, true, false>(a.S, a.Shi, sb, ns, b0, a.fragShift, sv, rr);
-          else groupLoad<LAYOUT, false, false>(a.S, a.Shi, sb, ns, b0, a.fragShift, sv, rr);
-        }
+        if (b0 + GJ_BATCH <= ns) groupLoad<LAYOUT, true, PRE_RID>(a.S, a.Shi, sb, ns, b0, a.fragShift, sv, rr);
+        else groupLoad<LAYOUT, false, PRE_RID>(a.S, a.Shi, sb, ns, b0, a.fragShift, sv, rr);
       }
       if constexpr (DIRECT) {
 #pragma unroll
@@ -288,9 +274,6 @@ __global__ __launch_bounds__(GJ_T, LAYOUT == MK_WIDE || SUM ? 2 : LAYOUT == MK_S
           if (b0 + k * GJ_T + t < ns) atomicAdd(&cnt[sv[k] & mask], 1u);  // (fragments are < 2^fragBits)
       } else {
         // G tuples at a time: their slots, then (SUM) all G gathers issued before the first value is consumed.
-        // (Wide tuples with a value column take 8, and read the rid -- the second word of the 16-byte tuple whose
-        // key they hold -- only for tuples with a slot: with 16 preloaded 8-byte rids next to 16 8-byte keys of
-        // either side the kernel spilled 52 bytes per lane to scratch.)
         constexpr int G = SUM && LAYOUT == MK_WIDE ? 8 : GJ_K;
 #pragma unroll
         for (int g0 = 0; g0 < GJ_K; g0 += G) {
@@ -324,7 +307,7 @@ __global__ __launch_bounds__(GJ_T, LAYOUT == MK_WIDE || SUM ? 2 : LAYOUT == MK_S
               if (slot[j] != GJ_NONE) {  // a tuple that found no slot forms no address
                 uint64_t rid;
                 if constexpr (!PRE_RID) rid = val[j];
-                else rid = LAYOUT == MK_COMPRESSED ? ((uint64_t)rr[g0 + j] & ridMask) : (uint64_t)rr[g0 + j];
+                else rid = groupRid<LAYOUT>(rr[g0 + j], ridMask);
                 val[j] = __builtin_nontemporal_load(values + (rid - ridOffset) * stride);
               }
             }
@@ -346,20 +329,13 @@ __global__ __launch_bounds__(GJ_T, LAYOUT == MK_WIDE || SUM ? 2 : LAYOUT == MK_S
     __syncthreads();
 
     // ---- inner side: count and sum of the first slot of every inner tuple's key
-    for (uint32_t b0 = 0; b0 < nr; b0 += BATCH) {
-      if (nr > BATCH) groupLoad<LAYOUT, false, false>(a.R, a.Rhi, rb, nr, b0, a.fragShift, rv, nor);  // else in registers
+    for (uint32_t b0 = 0; b0 < nr; b0 += GJ_BATCH) {
+      if (nr > GJ_BATCH) groupLoad<LAYOUT, false, false>(a.R, a.Rhi, rb, nr, b0, a.fragShift, rv, nor);  // else in registers
 #pragma unroll
       for (int k = 0; k < GJ_K; ++k) {
         const uint32_t idx = b0 + k * GJ_T + t;
         if (idx < nr) {
-          const K key = rv[k];
-          uint32_t h;
-          if constexpr (DIRECT) {
-            h = (uint32_t)key & mask;
-          } else {
-            h = groupHash<LAYOUT>(key, tbits);
-            while (table[h] != key) h = (h + 1) & mask;  // the key is in the table: this tuple inserted it
-          }
+          const uint32_t h = groupInnerSlot<LAYOUT, DIRECT>(table, rv[k], tbits, mask);
           const uint32_t c = cnt[h];
           if (c) {
             matches += c;
@@ -383,60 +359,22 @@ constexpr int groupAggBatch(int layout, int c) {
   return g >= 16 ? 16 : g >= 8 ? 8 : g >= 4 ? 4 : 2;
 }
 
-// The aggregate code is wave-uniform (a kernel argument): one scalar branch per atomic.
-// TYPED: so is the column's type.  A floating-point accumulator holds the bits of a binary64 and takes the f64
-// atomics (add, IEEE min, IEEE max); the integer types take the forms below.
-template <bool TYPED>
-__device__ __forceinline__ void groupAggLdsT(unsigned long long *p, unsigned long long v, uint32_t agg, uint32_t dtype);
-template <bool TYPED>
-__device__ __forceinline__ void groupAggGlobalT(unsigned long long *p, unsigned long long v, uint32_t agg,
-                                                uint32_t dtype);
-__device__ __forceinline__ void groupAggLds(unsigned long long *p, unsigned long long v, uint32_t agg) {
-  if (agg == GROUP_SUM)
-    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  else if (agg == GROUP_MIN)
-    __hip_atomic_fetch_min(reinterpret_cast<long long *>(p), (long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  else
-    __hip_atomic_fetch_max(reinterpret_cast<long long *>(p), (long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void groupAggGlobal(unsigned long long *p, unsigned long long v, uint32_t agg) {
-  if (agg == GROUP_SUM)
-    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else if (agg == GROUP_MIN)
-    __hip_atomic_fetch_min(reinterpret_cast<long long *>(p), (long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else
-    __hip_atomic_fetch_max(reinterpret_cast<long long *>(p), (long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <bool TYPED>
-__device__ __forceinline__ void groupAggLdsT(unsigned long long *p, unsigned long long v, uint32_t agg, uint32_t dtype) {
+// One accumulator update in LDS (SCOPE workgroup) or on the global accumulators (agent).  The aggregate code is
+// wave-uniform (a kernel argument): one scalar branch per atomic.  TYPED: so is the column's type; a floating-point
+// accumulator holds the bits of a binary64 and takes the f64 atomics (add, IEEE min, IEEE max).
+template <int SCOPE, bool TYPED>
+__device__ __forceinline__ void groupAggAtomic(unsigned long long *p, unsigned long long v, uint32_t agg, uint32_t dtype) {
   if (TYPED && groupDtypeIsFloat(dtype)) {
     double *d = reinterpret_cast<double *>(p);
     const double x = __longlong_as_double((long long)v);
-    if (agg == GROUP_SUM)
-      __hip_atomic_fetch_add(d, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else if (agg == GROUP_MIN)
-      __hip_atomic_fetch_min(d, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else
-      __hip_atomic_fetch_max(d, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (agg == GROUP_SUM) __hip_atomic_fetch_add(d, x, __ATOMIC_RELAXED, SCOPE);
+    else if (agg == GROUP_MIN) __hip_atomic_fetch_min(d, x, __ATOMIC_RELAXED, SCOPE);
+    else __hip_atomic_fetch_max(d, x, __ATOMIC_RELAXED, SCOPE);
   } else {
-    groupAggLds(p, v, agg);
-  }
-}
-template <bool TYPED>
-__device__ __forceinline__ void groupAggGlobalT(unsigned long long *p, unsigned long long v, uint32_t agg,
-                                                uint32_t dtype) {
-  if (TYPED && groupDtypeIsFloat(dtype)) {
-    double *d = reinterpret_cast<double *>(p);
-    const double x = __longlong_as_double((long long)v);
-    if (agg == GROUP_SUM)
-      __hip_atomic_fetch_add(d, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else if (agg == GROUP_MIN)
-      __hip_atomic_fetch_min(d, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else
-      __hip_atomic_fetch_max(d, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  } else {
-    groupAggGlobal(p, v, agg);
+    long long *i = reinterpret_cast<long long *>(p);
+    if (agg == GROUP_SUM) __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, SCOPE);
+    else if (agg == GROUP_MIN) __hip_atomic_fetch_min(i, (long long)v, __ATOMIC_RELAXED, SCOPE);
+    else __hip_atomic_fetch_max(i, (long long)v, __ATOMIC_RELAXED, SCOPE);
   }
 }
 
@@ -468,9 +406,6 @@ __global__ __launch_bounds__(GJ_T) void groupAggFillKernel(GroupColumns cols, un
   }
 }
 
-// bpGroupKernel<LAYOUT, false, true> with C accumulators per slot, each with its own column and aggregate.
-// TYPED = false: every column is int64 (the code of the kernel before the typed columns); TYPED = true: each
-// column has its own element type as well (cols.dtype), branched on in scalar code like the aggregate.
 template <int LAYOUT, int C, bool TYPED>
 __global__ __launch_bounds__(GJ_T, 2) void bpGroupAggKernel(BPArgs a, const BPItem *__restrict__ items,
                                                             const uint32_t *__restrict__ nItemsPtr, uint32_t capacity,
@@ -479,8 +414,7 @@ __global__ __launch_bounds__(GJ_T, 2) void bpGroupAggKernel(BPArgs a, const BPIt
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   using K = typename GroupKey<LAYOUT>::type;
   using R = typename GroupRid<LAYOUT>::type;
-  constexpr K EMPTY = LAYOUT == MK_WIDE ? (K)GJ_EMPTY64 : (K)GJ_EMPTY32;
-  constexpr uint32_t BATCH = GJ_T * GJ_K;
+  constexpr K EMPTY = GroupKey<LAYOUT>::EMPTY;
   constexpr bool PRE_RID = LAYOUT != MK_WIDE;  // wide tuples read their rid when a slot was found
   constexpr int G = groupAggBatch(LAYOUT, C);  // (TYPED holds the values as loaded: no more VGPRs, the same G)
   const uint64_t maxSlots = groupMaxSlots(a.rChunk);
@@ -510,9 +444,9 @@ __global__ __launch_bounds__(GJ_T, 2) void bpGroupAggKernel(BPArgs a, const BPIt
     // First inner batch and first outer batch are in flight while the table is cleared.
     K rv[GJ_K], sv[GJ_K];
     R rr[PRE_RID ? GJ_K : 1], nor[1];
-    if (nr >= BATCH) groupLoad<LAYOUT, true, false>(a.R, a.Rhi, rb, nr, 0, a.fragShift, rv, nor);
+    if (nr >= GJ_BATCH) groupLoad<LAYOUT, true, false>(a.R, a.Rhi, rb, nr, 0, a.fragShift, rv, nor);
     else groupLoad<LAYOUT, false, false>(a.R, a.Rhi, rb, nr, 0, a.fragShift, rv, nor);
-    if (ns >= BATCH) groupLoad<LAYOUT, true, PRE_RID>(a.S, a.Shi, sb, ns, 0, a.fragShift, sv, rr);
+    if (ns >= GJ_BATCH) groupLoad<LAYOUT, true, PRE_RID>(a.S, a.Shi, sb, ns, 0, a.fragShift, sv, rr);
     else groupLoad<LAYOUT, false, PRE_RID>(a.S, a.Shi, sb, ns, 0, a.fragShift, sv, rr);
     for (uint32_t i = t; i < slots; i += GJ_T) {
       cnt[i] = 0;
@@ -523,7 +457,7 @@ __global__ __launch_bounds__(GJ_T, 2) void bpGroupAggKernel(BPArgs a, const BPIt
     __syncthreads();
 
     // ---- build: every inner copy takes a slot
-    for (uint32_t b0 = 0; b0 < nr; b0 += BATCH) {
+    for (uint32_t b0 = 0; b0 < nr; b0 += GJ_BATCH) {
       if (b0) groupLoad<LAYOUT, false, false>(a.R, a.Rhi, rb, nr, b0, a.fragShift, rv, nor);
 #pragma unroll
       for (int k = 0; k < GJ_K; ++k) {
@@ -537,9 +471,9 @@ __global__ __launch_bounds__(GJ_T, 2) void bpGroupAggKernel(BPArgs a, const BPIt
     __syncthreads();
 
     // ---- probe: the first slot of the key, one u32 LDS atomic and one 64-bit LDS atomic per column
-    for (uint32_t b0 = 0; b0 < ns; b0 += BATCH) {
+    for (uint32_t b0 = 0; b0 < ns; b0 += GJ_BATCH) {
       if (b0) {
-        if (b0 + BATCH <= ns) groupLoad<LAYOUT, true, PRE_RID>(a.S, a.Shi, sb, ns, b0, a.fragShift, sv, rr);
+        if (b0 + GJ_BATCH <= ns) groupLoad<LAYOUT, true, PRE_RID>(a.S, a.Shi, sb, ns, b0, a.fragShift, sv, rr);
         else groupLoad<LAYOUT, false, PRE_RID>(a.S, a.Shi, sb, ns, b0, a.fragShift, sv, rr);
       }
       // G tuples at a time: their slots, then all C * G gathers issued before the first value is consumed.
@@ -576,7 +510,7 @@ __global__ __launch_bounds__(GJ_T, 2) void bpGroupAggKernel(BPArgs a, const BPIt
           if (slot[j] != GJ_NONE) {  // a tuple that found no slot forms no address
             uint64_t rid;
             if constexpr (!PRE_RID) rid = wrid[j];
-            else rid = LAYOUT == MK_COMPRESSED ? ((uint64_t)rr[g0 + j] & ridMask) : (uint64_t)rr[g0 + j];
+            else rid = groupRid<LAYOUT>(rr[g0 + j], ridMask);
             const uint64_t row = rid - cols.offset;
 #pragma unroll
             for (int c = 0; c < C; ++c) {
@@ -594,11 +528,11 @@ __global__ __launch_bounds__(GJ_T, 2) void bpGroupAggKernel(BPArgs a, const BPIt
             atomicAdd(&cnt[slot[j]], 1u);
 #pragma unroll
             for (int c = 0; c < C; ++c) {
-              if constexpr (TYPED)
-                groupAggLdsT<true>(&aggs[c * maxSlots + slot[j]], groupWiden(vlo[c][j], vhi[c][j], cols.dtype[c]),
-                                   cols.agg[c], cols.dtype[c]);
-              else
-                groupAggLds(&aggs[c * maxSlots + slot[j]], val[c][j], cols.agg[c]);
+              unsigned long long v;
+              if constexpr (TYPED) v = groupWiden(vlo[c][j], vhi[c][j], cols.dtype[c]);
+              else v = val[c][j];
+              groupAggAtomic<__HIP_MEMORY_SCOPE_WORKGROUP, TYPED>(&aggs[c * maxSlots + slot[j]], v, cols.agg[c],
+                                                                  cols.dtype[c]);
             }
           }
         }
@@ -607,27 +541,21 @@ __global__ __launch_bounds__(GJ_T, 2) void bpGroupAggKernel(BPArgs a, const BPIt
     __syncthreads();
 
     // ---- inner side: count and aggregates of the first slot of every inner tuple's key
-    for (uint32_t b0 = 0; b0 < nr; b0 += BATCH) {
-      if (nr > BATCH) groupLoad<LAYOUT, false, false>(a.R, a.Rhi, rb, nr, b0, a.fragShift, rv, nor);  // else in registers
+    for (uint32_t b0 = 0; b0 < nr; b0 += GJ_BATCH) {
+      if (nr > GJ_BATCH) groupLoad<LAYOUT, false, false>(a.R, a.Rhi, rb, nr, b0, a.fragShift, rv, nor);  // else in registers
 #pragma unroll
       for (int k = 0; k < GJ_K; ++k) {
         const uint32_t idx = b0 + k * GJ_T + t;
         if (idx < nr) {
-          const K key = rv[k];
-          uint32_t h = groupHash<LAYOUT>(key, tbits);
-          while (table[h] != key) h = (h + 1) & mask;  // the key is in the table: this tuple inserted it
+          const uint32_t h = groupInnerSlot<LAYOUT, false>(table, rv[k], tbits, mask);
           const uint32_t c0 = cnt[h];
           if (c0) {
             matches += c0;
             atomicAdd(&accCount[rb + idx], c0);
 #pragma unroll
-            for (int c = 0; c < C; ++c) {
-              if constexpr (TYPED)
-                groupAggGlobalT<true>(&accAgg[c * accSlots + rb + idx], aggs[c * maxSlots + h], cols.agg[c],
-                                      cols.dtype[c]);
-              else
-                groupAggGlobal(&accAgg[c * accSlots + rb + idx], aggs[c * maxSlots + h], cols.agg[c]);
-            }
+            for (int c = 0; c < C; ++c)
+              groupAggAtomic<__HIP_MEMORY_SCOPE_AGENT, TYPED>(&accAgg[c * accSlots + rb + idx], aggs[c * maxSlots + h],
+                                                              cols.agg[c], cols.dtype[c]);
           }
         }
       }
@@ -650,63 +578,14 @@ __global__ __launch_bounds__(GJ_T) void groupUnitLengthsKernel(BPArgs a, const M
   }
 }
 
-// One wave per unit of a.S (the inner relation: sides swapped by the caller).
-template <int LAYOUT, bool SUM>
+// One wave per unit of a.S (the inner relation: sides swapped by the caller); rows of W = 2 + C words.
+template <int LAYOUT, int C>
 __global__ __launch_bounds__(GJ_T) void groupEmitKernel(BPArgs a, const MarkUnit *__restrict__ units,
                                                        const uint32_t *__restrict__ nUnitsPtr, uint32_t capacity,
                                                        const uint32_t *__restrict__ accCount,
-                                                       const unsigned long long *__restrict__ accSum,
+                                                       const unsigned long long *__restrict__ accAgg, uint64_t accSlots,
                                                        const unsigned long long *__restrict__ unitOffsets,
                                                        unsigned long long *__restrict__ out, uint64_t outCapacity) {
-  constexpr uint32_t W = SUM ? 3 : 2;
-  __shared__ unsigned long long wsum[GJ_T / WAVE];
-  const uint32_t lane = threadIdx.x & (WAVE - 1);
-  const uint64_t ridMask = a.keyShift >= 64 ? ~0ull : ((1ull << a.keyShift) - 1);
-  const uint32_t nUnits = min(*nUnitsPtr, capacity);
-  const uint32_t wavesPerGrid = gridDim.x * (GJ_T / WAVE);
-  unsigned long long zeros = 0;
-  for (uint32_t u = blockIdx.x * (GJ_T / WAVE) + threadIdx.x / WAVE; u < nUnits; u += wavesPerGrid) {
-    uint64_t ub, ue;
-    unitRange(a, units[u], ub, ue);
-    const unsigned long long base = out ? unitOffsets[u] : 0ull;
-    for (uint64_t p0 = ub; p0 < ue; p0 += WAVE) {  // wave-uniform
-      const uint32_t m = (uint32_t)min((uint64_t)WAVE, ue - p0);
-      const bool valid = lane < m;
-      const uint32_t c = valid ? accCount[p0 + lane] : 1u;
-      zeros += c == 0;
-      if (!out) continue;
-      const unsigned long long row0 = base + (p0 - ub);  // the wave's first output row
-      const unsigned long long rid = valid ? markRid<LAYOUT>(a, p0 + lane, ridMask) : 0ull;
-      if constexpr (!SUM) {
-        if (valid && row0 + lane < outCapacity)
-          reinterpret_cast<ulonglong2 *>(out)[row0 + lane] = make_ulonglong2(rid, (unsigned long long)c);
-      } else {
-        const unsigned long long s = valid ? accSum[p0 + lane] : 0ull;
-        // word q of the run (row q / 3, column q % 3) is stored by lane q % 64: consecutive 8-byte stores
-#pragma unroll
-        for (uint32_t k = 0; k < W; ++k) {
-          const uint32_t q = WAVE * k + lane, src = q / W, col = q - src * W;
-          const unsigned long long vr = __shfl(rid, src, WAVE), vs = __shfl(s, src, WAVE);
-          const uint32_t vc = __shfl(c, src, WAVE);
-          const unsigned long long v = col == 0 ? vr : col == 1 ? (unsigned long long)vc : vs;
-          if (src < m && row0 + src < outCapacity) out[row0 * W + q] = v;
-        }
-      }
-    }
-  }
-  const unsigned long long total = blockReduceSum<GJ_T, unsigned long long>(zeros, wsum);
-  if (threadIdx.x == 0 && total) atomicAdd(a.result, total);
-}
-
-// groupEmitKernel<LAYOUT, true> with C aggregate words per row: W = 2 + C (4 to 6; one column takes groupEmitKernel).
-template <int LAYOUT, int C>
-__global__ __launch_bounds__(GJ_T) void groupEmitAggKernel(BPArgs a, const MarkUnit *__restrict__ units,
-                                                          const uint32_t *__restrict__ nUnitsPtr, uint32_t capacity,
-                                                          const uint32_t *__restrict__ accCount,
-                                                          const unsigned long long *__restrict__ accAgg,
-                                                          uint64_t accSlots,
-                                                          const unsigned long long *__restrict__ unitOffsets,
-                                                          unsigned long long *__restrict__ out, uint64_t outCapacity) {
   constexpr uint32_t W = 2 + C;
   __shared__ unsigned long long wsum[GJ_T / WAVE];
   const uint32_t lane = threadIdx.x & (WAVE - 1);
@@ -726,22 +605,27 @@ __global__ __launch_bounds__(GJ_T) void groupEmitAggKernel(BPArgs a, const MarkU
       if (!out) continue;
       const unsigned long long row0 = base + (p0 - ub);  // the wave's first output row
       const unsigned long long rid = valid ? markRid<LAYOUT>(a, p0 + lane, ridMask) : 0ull;
-      unsigned long long g[C];
+      if constexpr (C == 0) {
+        if (valid && row0 + lane < outCapacity)
+          reinterpret_cast<ulonglong2 *>(out)[row0 + lane] = make_ulonglong2(rid, (unsigned long long)c);
+      } else {
+        unsigned long long g[C];
 #pragma unroll
-      for (int j = 0; j < C; ++j) g[j] = valid ? accAgg[j * accSlots + p0 + lane] : 0ull;
-      // word q of the run (row q / W, column q % W) is stored by lane q % 64: consecutive 8-byte stores
+        for (int j = 0; j < C; ++j) g[j] = valid ? accAgg[j * accSlots + p0 + lane] : 0ull;
+        // word q of the run (row q / W, column q % W) is stored by lane q % 64: consecutive 8-byte stores
 #pragma unroll
-      for (uint32_t k = 0; k < W; ++k) {
-        const uint32_t q = WAVE * k + lane, src = q / W, col = q - src * W;
-        const unsigned long long vr = __shfl(rid, src, WAVE);
-        const uint32_t vc = __shfl(c, src, WAVE);
-        unsigned long long v = col == 0 ? vr : (unsigned long long)vc;
+        for (uint32_t k = 0; k < W; ++k) {
+          const uint32_t q = WAVE * k + lane, src = q / W, col = q - src * W;
+          const unsigned long long vr = __shfl(rid, src, WAVE);
+          const uint32_t vc = __shfl(c, src, WAVE);
+          unsigned long long v = col == 0 ? vr : (unsigned long long)vc;
 #pragma unroll
-        for (int j = 0; j < C; ++j) {
-          const unsigned long long vg = __shfl(g[j], src, WAVE);
-          if (col == 2u + j) v = vg;
+          for (int j = 0; j < C; ++j) {
+            const unsigned long long vg = __shfl(g[j], src, WAVE);
+            if (col == 2u + j) v = vg;
+          }
+          if (src < m && row0 + src < outCapacity) out[row0 * W + q] = v;
         }
-        if (src < m && row0 + src < outCapacity) out[row0 * W + q] = v;
       }
     }
   }
@@ -749,108 +633,25 @@ __global__ __launch_bounds__(GJ_T) void groupEmitAggKernel(BPArgs a, const MarkU
   if (threadIdx.x == 0 && total) atomicAdd(a.result, total);
 }
 
+// --------------------------------------------------------------- launchers
 // Small units are latency-bound per wave: the grid fills every CU with waves (as semi_join.hip).
 static uint32_t groupUnitGrid(uint32_t capacity) {
   const uint32_t perBlock = GJ_T / WAVE;
   return std::max<uint32_t>(1, std::min<uint32_t>(256 * 8, (capacity + perBlock - 1) / perBlock));
 }
 
-static BPArgs groupArgs(const BPArgs &args) {
+// The arguments with both end arrays set, after the checks every group kernel needs.
+static BPArgs groupArgs(const BPArgs &args, const char *who) {
   BPArgs a = args;
   if (!a.partREnd) a.partREnd = a.partR + 1;
   if (!a.partSEnd) a.partSEnd = a.partS + 1;
+  HJ_CHECK(!a.keyOnly, "%s: key-only words carry no rid (group joins use rid-carrying layouts)", who);
+  HJ_CHECK(!(a.split && a.wide), "%s: the split layout holds compressed tuples", who);
   return a;
 }
 
-size_t bpGroupLdsBytes(const BPArgs &a, uint32_t columns) {
-  if (groupDirect(a, columns != 0)) return (size_t(4) << a.fragBits) + 64;
-  return groupTableBytes(a.rChunk, a.wide, columns);
-}
-
-void bpGroup(const BPArgs &args, const BPItem *items, const uint32_t *nItems, uint32_t capacity,
-             const unsigned long long *values, uint64_t ridOffset, uint64_t strideWords, uint32_t *accCount,
-             unsigned long long *accSum, hipStream_t s) {
-  if (capacity == 0) return;
-  const BPArgs a = groupArgs(args);
-  const bool sum = values != nullptr;
-  const size_t lds = bpGroupLdsBytes(a, sum ? 1 : 0);
-  HJ_CHECK(lds <= 160 * 1024, "bpGroup: LDS request %zu exceeds 160 KiB (rChunk=%u%s)", lds, a.rChunk,
-           sum ? ", with a value column" : "");
-  HJ_CHECK(!a.keyOnly, "bpGroup: key-only words carry no rid (group joins use rid-carrying layouts)");
-  HJ_CHECK(!(a.split && a.wide), "bpGroup: the split layout holds compressed tuples");
-  HJ_CHECK(!a.split || (a.Rhi && a.Shi), "bpGroup: split layout without fragment columns");
-  HJ_CHECK(a.wide || a.fragShift >= 32, "bpGroup: fragShift=%u < 32 (the rid field of a CompressedTuple is >= 32 bits)",
-           a.fragShift);
-  HJ_CHECK(a.result && accCount, "bpGroup: needs the pair counter and the count accumulators");
-  HJ_CHECK(!sum || (accSum && strideWords >= 1), "bpGroup: a value column needs the sum accumulators and a stride >= 1");
-  const size_t bound = a.wide || sum ? 2 : a.split ? 4 : 3;
-  const uint32_t perCu = (uint32_t)std::max<size_t>(1, std::min<size_t>(bound, (160 * 1024) / lds));
-  const uint32_t blocks = std::min<uint32_t>(capacity, 256 * perCu);
-#define HJ_GJ(LAYOUT, DIRECT, SUM)                                                                                 \
-  hipLaunchKernelGGL((bpGroupKernel<LAYOUT, DIRECT, SUM>), dim3(blocks), dim3(GJ_T), lds, s, a, items, nItems, capacity, \
-                     values, ridOffset, strideWords, accCount, accSum)
-  const bool direct = groupDirect(a, sum);
-  switch (markLayout(a)) {
-    case MK_COMPRESSED:
-      if (sum) HJ_GJ(MK_COMPRESSED, false, true);
-      else if (direct) HJ_GJ(MK_COMPRESSED, true, false);
-      else HJ_GJ(MK_COMPRESSED, false, false);
-      break;
-    case MK_SPLIT:
-      if (sum) HJ_GJ(MK_SPLIT, false, true);
-      else if (direct) HJ_GJ(MK_SPLIT, true, false);
-      else HJ_GJ(MK_SPLIT, false, false);
-      break;
-    default:
-      if (sum) HJ_GJ(MK_WIDE, false, true);
-      else HJ_GJ(MK_WIDE, false, false);
-      break;
-  }
-#undef HJ_GJ
-  HIP_CHECK_LAUNCH();
-}
-
-void groupUnitLengths(const BPArgs &args, const MarkUnit *units, const uint32_t *nUnits, uint32_t capacity,
-                      uint32_t *unitCounts, hipStream_t s) {
-  if (capacity == 0) return;
-  const BPArgs a = groupArgs(args);
-  const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>(1024, (capacity + GJ_T - 1) / GJ_T));
-  hipLaunchKernelGGL(groupUnitLengthsKernel, dim3(blocks), dim3(GJ_T), 0, s, a, units, nUnits, capacity, unitCounts);
-  HIP_CHECK_LAUNCH();
-}
-
-void groupEmit(const BPArgs &args, const MarkUnit *units, const uint32_t *nUnits, uint32_t capacity,
-               const uint32_t *accCount, const unsigned long long *accSum, const unsigned long long *unitOffsets,
-               unsigned long long *out, uint64_t outCapacity, hipStream_t s) {
-  if (capacity == 0) return;
-  const BPArgs a = groupArgs(args);
-  HJ_CHECK(!a.keyOnly, "groupEmit: key-only words carry no rid");
-  HJ_CHECK(!(a.split && a.wide), "groupEmit: the split layout holds compressed tuples");
-  HJ_CHECK(a.result && accCount, "groupEmit: needs the empty-group counter and the count accumulators");
-  HJ_CHECK(!out || unitOffsets, "groupEmit: rows need the unit offsets");
-  HJ_CHECK(!out || reinterpret_cast<uintptr_t>(out) % 16 == 0, "groupEmit: the rows must be 16-byte aligned");
-  const dim3 grid(groupUnitGrid(capacity)), block(GJ_T);
-#define HJ_GJ_EMIT(LAYOUT, SUM)                                                                                    \
-  hipLaunchKernelGGL((groupEmitKernel<LAYOUT, SUM>), grid, block, 0, s, a, units, nUnits, capacity, accCount, accSum, \
-                     unitOffsets, out, outCapacity)
-  const bool sum = accSum != nullptr;
-  switch (markLayout(a)) {
-    case MK_COMPRESSED:
-      if (sum) HJ_GJ_EMIT(MK_COMPRESSED, true); else HJ_GJ_EMIT(MK_COMPRESSED, false);
-      break;
-    case MK_SPLIT:
-      if (sum) HJ_GJ_EMIT(MK_SPLIT, true); else HJ_GJ_EMIT(MK_SPLIT, false);
-      break;
-    default:
-      if (sum) HJ_GJ_EMIT(MK_WIDE, true); else HJ_GJ_EMIT(MK_WIDE, false);
-      break;
-  }
-#undef HJ_GJ_EMIT
-  HIP_CHECK_LAUNCH();
-}
-
 static void groupColumnsCheck(const GroupColumns &cols, const char *who) {
-  HJ_CHECK(cols.n >= 1 && cols.n <= GROUP_MAX_COLUMNS, "%s: %u value columns (1 to %u)", who, cols.n, GROUP_MAX_COLUMNS);
+  HJ_CHECK(cols.n <= GROUP_MAX_COLUMNS, "%s: %u value columns (0 to %u)", who, cols.n, GROUP_MAX_COLUMNS);
   for (uint32_t c = 0; c < cols.n; ++c)
     HJ_CHECK(cols.col[c] && cols.stride[c] >= 1 && cols.agg[c] <= GROUP_MAX && cols.dtype[c] <= GROUP_DTYPE_MAX &&
                  reinterpret_cast<uintptr_t>(cols.col[c]) % groupDtypeBytes(cols.dtype[c]) == 0,
@@ -859,95 +660,115 @@ static void groupColumnsCheck(const GroupColumns &cols, const char *who) {
              who, c);
 }
 
-void groupAggFill(const GroupColumns &cols, unsigned long long *accAgg, uint64_t accSlots, hipStream_t s) {
-  if (accSlots == 0) return;
-  groupColumnsCheck(cols, "groupAggFill");
-  HJ_CHECK(accAgg, "groupAggFill: needs the accumulators");
+size_t bpGroupLdsBytes(const BPArgs &a, uint32_t columns) {
+  if (groupDirect(a, columns != 0)) return (size_t(4) << a.fragBits) + 64;
+  return groupTableBytes(a.rChunk, a.wide, columns);
+}
+
+void groupAggInit(const GroupColumns &cols, unsigned long long *accAgg, uint64_t accSlots, hipStream_t s) {
+  if (cols.n == 0 || accSlots == 0) return;
+  groupColumnsCheck(cols, "groupAggInit");
+  HJ_CHECK(accAgg, "groupAggInit: needs the accumulators");
+  bool zero = true;
+  for (uint32_t c = 0; c < cols.n; ++c) zero = zero && groupAggIdentity(cols.agg[c], cols.dtype[c]) == 0;
+  if (zero) {  // (the engine's own clear, as ExecContext::zero)
+    zeroWords(accAgg, cols.n * accSlots, s);
+    return;
+  }
   const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(256 * 8, (accSlots + GJ_T - 1) / GJ_T));
   hipLaunchKernelGGL(groupAggFillKernel, dim3(blocks), dim3(GJ_T), 0, s, cols, accAgg, accSlots);
   HIP_CHECK_LAUNCH();
 }
 
-void bpGroupAgg(const BPArgs &args, const BPItem *items, const uint32_t *nItems, uint32_t capacity,
-                const GroupColumns &cols, uint32_t *accCount, unsigned long long *accAgg, uint64_t accSlots,
-                hipStream_t s) {
+void bpGroup(const BPArgs &args, const BPItem *items, const uint32_t *nItems, uint32_t capacity,
+             const GroupColumns &cols, uint32_t *accCount, unsigned long long *accAgg, uint64_t accSlots,
+             hipStream_t s) {
   if (capacity == 0) return;
-  groupColumnsCheck(cols, "bpGroupAgg");
-  const bool typed = groupColumnsTyped(cols);
-  if (cols.n == 1 && cols.agg[0] == GROUP_SUM && !typed) {  // the single-column kernel (identity 0: the fill zeroed it)
-    bpGroup(args, items, nItems, capacity, static_cast<const unsigned long long *>(cols.col[0]), cols.offset,
-            cols.stride[0], accCount, accAgg, s);
-    return;
-  }
-  const BPArgs a = groupArgs(args);
+  groupColumnsCheck(cols, "bpGroup");
+  const BPArgs a = groupArgs(args, "bpGroup");
   const size_t lds = bpGroupLdsBytes(a, cols.n);
-  HJ_CHECK(lds <= 160 * 1024, "bpGroupAgg: LDS request %zu exceeds 160 KiB (rChunk=%u, %u value columns)", lds, a.rChunk,
+  HJ_CHECK(lds <= 160 * 1024, "bpGroup: LDS request %zu exceeds 160 KiB (rChunk=%u, %u value columns)", lds, a.rChunk,
            cols.n);
-  HJ_CHECK(!a.keyOnly, "bpGroupAgg: key-only words carry no rid (group joins use rid-carrying layouts)");
-  HJ_CHECK(!(a.split && a.wide), "bpGroupAgg: the split layout holds compressed tuples");
-  HJ_CHECK(!a.split || (a.Rhi && a.Shi), "bpGroupAgg: split layout without fragment columns");
-  HJ_CHECK(a.wide || a.fragShift >= 32, "bpGroupAgg: fragShift=%u < 32 (the rid field of a CompressedTuple is >= 32 bits)",
+  HJ_CHECK(!a.split || (a.Rhi && a.Shi), "bpGroup: split layout without fragment columns");
+  HJ_CHECK(a.wide || a.fragShift >= 32, "bpGroup: fragShift=%u < 32 (the rid field of a CompressedTuple is >= 32 bits)",
            a.fragShift);
-  HJ_CHECK(a.result && accCount && accAgg, "bpGroupAgg: needs the pair counter and the accumulators");
-  const uint32_t perCu = (uint32_t)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / lds));
-  const uint32_t blocks = std::min<uint32_t>(capacity, 256 * perCu);
-#define HJ_GJ_AGG_T(LAYOUT, C, TYPED)                                                                          \
-  hipLaunchKernelGGL((bpGroupAggKernel<LAYOUT, C, TYPED>), dim3(blocks), dim3(GJ_T), lds, s, a, items, nItems, capacity, \
-                     cols, accCount, accAgg, accSlots)
-#define HJ_GJ_AGG(LAYOUT, C)            \
-  if (typed) HJ_GJ_AGG_T(LAYOUT, C, true); \
-  else HJ_GJ_AGG_T(LAYOUT, C, false)
-#define HJ_GJ_AGG_C(LAYOUT)                   \
-  switch (cols.n) {                           \
-    case 1: HJ_GJ_AGG(LAYOUT, 1); break;      \
-    case 2: HJ_GJ_AGG(LAYOUT, 2); break;      \
-    case 3: HJ_GJ_AGG(LAYOUT, 3); break;      \
-    default: HJ_GJ_AGG(LAYOUT, 4); break;     \
-  }
+  HJ_CHECK(a.result && accCount && (cols.n == 0 || accAgg), "bpGroup: needs the pair counter and the accumulators");
+  const bool typed = groupColumnsTyped(cols);
+  // No column, or one int64 SUM: the kernel without run-time aggregate branches.
+  const bool single = cols.n == 0 || (cols.n == 1 && cols.agg[0] == GROUP_SUM && !typed);
+  const bool direct = groupDirect(a, cols.n != 0);
+  const size_t bound = a.wide || cols.n ? 2 : a.split ? 4 : 3;  // the kernels' launch bounds
+  const uint32_t perCu = (uint32_t)std::max<size_t>(1, std::min<size_t>(bound, (160 * 1024) / lds));
+  const dim3 grid(std::min<uint32_t>(capacity, 256 * perCu)), block(GJ_T);
+#define HJ_GJ(LAYOUT, DIRECT, SUM)                                                                            \
+  hipLaunchKernelGGL((bpGroupKernel<LAYOUT, DIRECT, SUM>), grid, block, lds, s, a, items, nItems, capacity,    \
+                     static_cast<const unsigned long long *>(cols.col[0]), cols.offset, cols.stride[0], accCount, \
+                     accAgg)
+#define HJ_GJ_AGG(LAYOUT, C, TYPED)                                                                                 \
+  hipLaunchKernelGGL((bpGroupAggKernel<LAYOUT, C, TYPED>), grid, block, lds, s, a, items, nItems, capacity, cols, \
+                     accCount, accAgg, accSlots)
+#define HJ_GJ_AGG_C(LAYOUT, C)           \
+  if (typed) HJ_GJ_AGG(LAYOUT, C, true); \
+  else HJ_GJ_AGG(LAYOUT, C, false)
+#define HJ_GJ_LAYOUT(LAYOUT, DIRECT_BUILT)                                   \
+  if (single && cols.n) HJ_GJ(LAYOUT, false, true);                          \
+  else if (single && direct) HJ_GJ(LAYOUT, DIRECT_BUILT, false);             \
+  else if (single) HJ_GJ(LAYOUT, false, false);                              \
+  else if (cols.n == 1) { HJ_GJ_AGG_C(LAYOUT, 1); }                          \
+  else if (cols.n == 2) { HJ_GJ_AGG_C(LAYOUT, 2); }                          \
+  else if (cols.n == 3) { HJ_GJ_AGG_C(LAYOUT, 3); }                          \
+  else { HJ_GJ_AGG_C(LAYOUT, 4); }
   switch (markLayout(a)) {
-    case MK_COMPRESSED: HJ_GJ_AGG_C(MK_COMPRESSED); break;
-    case MK_SPLIT: HJ_GJ_AGG_C(MK_SPLIT); break;
-    default: HJ_GJ_AGG_C(MK_WIDE); break;
+    case MK_COMPRESSED: HJ_GJ_LAYOUT(MK_COMPRESSED, true); break;
+    case MK_SPLIT: HJ_GJ_LAYOUT(MK_SPLIT, true); break;
+    default: HJ_GJ_LAYOUT(MK_WIDE, false); break;  // (groupDirect is false for wide tuples)
   }
+#undef HJ_GJ_LAYOUT
 #undef HJ_GJ_AGG_C
 #undef HJ_GJ_AGG
-#undef HJ_GJ_AGG_T
+#undef HJ_GJ
   HIP_CHECK_LAUNCH();
 }
 
-void groupEmitAgg(const BPArgs &args, const MarkUnit *units, const uint32_t *nUnits, uint32_t capacity,
-                  const uint32_t *accCount, const unsigned long long *accAgg, uint64_t accSlots, uint32_t columns,
-                  const unsigned long long *unitOffsets, unsigned long long *out, uint64_t outCapacity, hipStream_t s) {
+void groupUnitLengths(const BPArgs &args, const MarkUnit *units, const uint32_t *nUnits, uint32_t capacity,
+                      uint32_t *unitCounts, hipStream_t s) {
   if (capacity == 0) return;
-  HJ_CHECK(columns >= 1 && columns <= GROUP_MAX_COLUMNS, "groupEmitAgg: %u value columns (1 to %u)", columns,
-           GROUP_MAX_COLUMNS);
-  HJ_CHECK(accAgg, "groupEmitAgg: needs the aggregate accumulators");
-  if (columns == 1) {  // (rid, count, aggregate): the three-word rows of groupEmit
-    groupEmit(args, units, nUnits, capacity, accCount, accAgg, unitOffsets, out, outCapacity, s);
-    return;
-  }
-  const BPArgs a = groupArgs(args);
-  HJ_CHECK(!a.keyOnly, "groupEmitAgg: key-only words carry no rid");
-  HJ_CHECK(!(a.split && a.wide), "groupEmitAgg: the split layout holds compressed tuples");
-  HJ_CHECK(a.result && accCount, "groupEmitAgg: needs the empty-group counter and the count accumulators");
-  HJ_CHECK(!out || unitOffsets, "groupEmitAgg: rows need the unit offsets");
+  const BPArgs a = groupArgs(args, "groupUnitLengths");
+  const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>(1024, (capacity + GJ_T - 1) / GJ_T));
+  hipLaunchKernelGGL(groupUnitLengthsKernel, dim3(blocks), dim3(GJ_T), 0, s, a, units, nUnits, capacity, unitCounts);
+  HIP_CHECK_LAUNCH();
+}
+
+void groupEmit(const BPArgs &args, const MarkUnit *units, const uint32_t *nUnits, uint32_t capacity,
+               const uint32_t *accCount, const unsigned long long *accAgg, uint64_t accSlots, uint32_t columns,
+               const unsigned long long *unitOffsets, unsigned long long *out, uint64_t outCapacity, hipStream_t s) {
+  if (capacity == 0) return;
+  HJ_CHECK(columns <= GROUP_MAX_COLUMNS, "groupEmit: %u value columns (0 to %u)", columns, GROUP_MAX_COLUMNS);
+  const BPArgs a = groupArgs(args, "groupEmit");
+  HJ_CHECK(a.result && accCount && (columns == 0 || accAgg),
+           "groupEmit: needs the empty-group counter and the accumulators");
+  HJ_CHECK(!out || unitOffsets, "groupEmit: rows need the unit offsets");
+  HJ_CHECK(!out || columns || reinterpret_cast<uintptr_t>(out) % 16 == 0,
+           "groupEmit: rows of (rid, count) must be 16-byte aligned");
   const dim3 grid(groupUnitGrid(capacity)), block(GJ_T);
-#define HJ_GJ_EMIT_AGG(LAYOUT, C)                                                                                      \
-  hipLaunchKernelGGL((groupEmitAggKernel<LAYOUT, C>), grid, block, 0, s, a, units, nUnits, capacity, accCount, accAgg, \
+#define HJ_GJ_EMIT(LAYOUT, C)                                                                                         \
+  hipLaunchKernelGGL((groupEmitKernel<LAYOUT, C>), grid, block, 0, s, a, units, nUnits, capacity, accCount, accAgg, \
                      accSlots, unitOffsets, out, outCapacity)
-#define HJ_GJ_EMIT_AGG_C(LAYOUT)                   \
-  switch (columns) {                               \
-    case 2: HJ_GJ_EMIT_AGG(LAYOUT, 2); break;      \
-    case 3: HJ_GJ_EMIT_AGG(LAYOUT, 3); break;      \
-    default: HJ_GJ_EMIT_AGG(LAYOUT, 4); break;     \
+#define HJ_GJ_EMIT_C(LAYOUT)                 \
+  switch (columns) {                         \
+    case 0: HJ_GJ_EMIT(LAYOUT, 0); break;    \
+    case 1: HJ_GJ_EMIT(LAYOUT, 1); break;    \
+    case 2: HJ_GJ_EMIT(LAYOUT, 2); break;    \
+    case 3: HJ_GJ_EMIT(LAYOUT, 3); break;    \
+    default: HJ_GJ_EMIT(LAYOUT, 4); break;   \
   }
   switch (markLayout(a)) {
-    case MK_COMPRESSED: HJ_GJ_EMIT_AGG_C(MK_COMPRESSED); break;
-    case MK_SPLIT: HJ_GJ_EMIT_AGG_C(MK_SPLIT); break;
-    default: HJ_GJ_EMIT_AGG_C(MK_WIDE); break;
+    case MK_COMPRESSED: HJ_GJ_EMIT_C(MK_COMPRESSED); break;
+    case MK_SPLIT: HJ_GJ_EMIT_C(MK_SPLIT); break;
+    default: HJ_GJ_EMIT_C(MK_WIDE); break;
   }
-#undef HJ_GJ_EMIT_AGG_C
-#undef HJ_GJ_EMIT_AGG
+#undef HJ_GJ_EMIT_C
+#undef HJ_GJ_EMIT
   HIP_CHECK_LAUNCH();
 }
 

@@ -498,16 +498,8 @@ struct RowSink {
   uint64_t *out = nullptr;  // [capacity][10] u64
   uint64_t capacity = 0;
 };
-// Outer value column of a group join with a sum (HashJoin::setGroupValues):
-// the value of rid r is values[(r - offset) * strideWords], rids [offset, offset + rows).
-struct GroupValues {
-  const uint64_t *values = nullptr;
-  uint64_t offset = 0;
-  uint64_t rows = 0;
-  uint64_t strideWords = 1;
-};
-// Outer value columns of a group join with aggregates (HashJoin::setGroupColumns):
-// n = 1 ... GROUP_MAX_COLUMNS columns, each a 1-D view with its own base
+// Outer value columns of a group join (HashJoin::setGroupColumns): n = 0 (count
+// only) ... GROUP_MAX_COLUMNS columns, each a 1-D view with its own base
 // pointer, element type (GroupDtype), positive element stride (in elements of
 // that type) and aggregate; column c's value of rid r is element
 // (r - offset) * stride[c] of col[c], rids [offset, offset + rows).
@@ -656,11 +648,11 @@ void markPlacePairs(const BPArgs &a, const MarkUnit *units, const uint32_t *nUni
                     uint64_t outCapacity, hipStream_t s);
 
 // Group joins (group_join.hip; core::JoinKind::Group): per inner tuple the
-// number of outer tuples with its key and, with a value column, the int64 sum
-// (wrapping) of values[(rid - ridOffset) * strideWords] over those tuples.
+// number of outer tuples with its key and the aggregates of cols.n = 0 ...
+// GROUP_MAX_COLUMNS outer value columns over those tuples (see GroupColumns
+// for the arithmetic).
 // Slots of the largest hashed table of a launch, and its LDS bytes: 4- or
-// 8-byte keys, a u32 counter and `columns` u64 accumulators per slot (0 = counts
-// only, 1 = a sum or one aggregate, up to GROUP_MAX_COLUMNS), plus the
+// 8-byte keys, a u32 counter and `columns` u64 accumulators per slot, plus the
 // reduction words.  Inline: the planner sizes rChunk with it (core::makePlan).
 HJ_HD uint64_t groupMaxSlots(uint32_t rChunk) {
   uint32_t b = 6;
@@ -670,52 +662,41 @@ HJ_HD uint64_t groupMaxSlots(uint32_t rChunk) {
 HJ_HD size_t groupTableBytes(uint32_t rChunk, bool wide, uint32_t columns) {
   return (size_t)(groupMaxSlots(rChunk) * ((wide ? 8 : 4) + 4 + 8 * (size_t)columns) + 64);
 }
-// The LDS request of bpGroup / bpGroupAgg (direct-addressed counts when there
-// is no value column and the fragments have at most 13 bits; the hashed table
-// with `columns` accumulators per slot otherwise).
+// The LDS request of bpGroup (direct-addressed counts when there is no value
+// column and the fragments have at most 13 bits; the hashed table with
+// `columns` accumulators per slot otherwise).
 size_t bpGroupLdsBytes(const BPArgs &a, uint32_t columns);
-// Over the BPItem list of bpPlanCounts / bpEmit.  accCount (u32) and accSum
-// (u64, only read with values) are indexed by the position in the partitioned
-// inner buffer and zeroed by the caller; every item adds its outer chunk's
-// count and sum of each inner tuple's key (global atomics), and the pairs
-// (the sum of all counts) to *a.result.  values == null: counts only, reads
-// no rid.  The caller guarantees fewer than 2^32 outer tuples per key.
+// Every column's identity into its accSlots accumulators before a bpGroup
+// launch: a stream-ordered clear (zeroWords) when all identities are zero bits
+// (every SUM; +0.0 too), a fill kernel otherwise (MIN and MAX).  cols.n == 0:
+// nothing.
+void groupAggInit(const GroupColumns &cols, unsigned long long *accAgg, uint64_t accSlots, hipStream_t s);
+// Over the BPItem list of bpPlanCounts / bpEmit.  accCount (u32, zeroed by the
+// caller) is indexed by the position in the partitioned inner buffer; accAgg
+// (read only with columns) is column-major, accAgg[c * accSlots + position], 8
+// bytes per accumulator whatever the column's type (int64, or the bits of a
+// binary64), and holds the identities (groupAggInit).  Every item applies its
+// outer chunk's count and aggregates of each inner tuple's key (global
+// atomics), and adds the pairs (the sum of all counts) to *a.result.  cols.n
+// == 0 reads no rid.  accAgg must be coarse-grained device memory (hipMalloc):
+// the floating-point atomics are hardware atomics only there.  The caller
+// guarantees fewer than 2^32 outer tuples per key.  The launcher picks the
+// kernel: no column or one int64 SUM column, all-int64 columns, typed columns.
+// An LDS request above 160 KiB is refused.
 // Layouts: CompressedTuples, split columns, wide tuples (not key-only words).
-void bpGroup(const BPArgs &a, const BPItem *items, const uint32_t *nItems, uint32_t capacity,
-             const unsigned long long *values, uint64_t ridOffset, uint64_t strideWords, uint32_t *accCount,
-             unsigned long long *accSum, hipStream_t s);
+void bpGroup(const BPArgs &a, const BPItem *items, const uint32_t *nItems, uint32_t capacity, const GroupColumns &cols,
+             uint32_t *accCount, unsigned long long *accAgg, uint64_t accSlots, hipStream_t s);
 // Over the units of a.S (the inner side: outerSwapSides): unitCounts[u] = the
 // unit's length (every position is a group).
 void groupUnitLengths(const BPArgs &a, const MarkUnit *units, const uint32_t *nUnits, uint32_t capacity,
                       uint32_t *unitCounts, hipStream_t s);
-// Rows (rid, count) -- with accSum (rid, count, sum) -- of unit u's positions,
-// in position order from out[unitOffsets[u] * W] (W = 2 or 3 words; rows at or
-// beyond outCapacity are not stored); the groups with count 0 are added to
+// Rows (rid, count, agg_0, ..., agg_{columns-1}) of unit u's positions, W = 2 +
+// columns words each, in position order from out[unitOffsets[u] * W] (rows at
+// or beyond outCapacity are not stored); the groups with count 0 are added to
 // *a.result.  out == null: only counts them.
 void groupEmit(const BPArgs &a, const MarkUnit *units, const uint32_t *nUnits, uint32_t capacity,
-               const uint32_t *accCount, const unsigned long long *accSum, const unsigned long long *unitOffsets,
-               unsigned long long *out, uint64_t outCapacity, hipStream_t s);
-
-// Group joins with aggregates: cols.n = 1 ... GROUP_MAX_COLUMNS value columns,
-// each int64, int32, float64 or float32 (GroupDtype) and each summed, or
-// reduced to its minimum or maximum (see GroupColumns for the arithmetic).
-// accCount as bpGroup; accAgg is column-major, accAgg[c * accSlots + position],
-// 8 bytes per accumulator whatever the column's type (int64, or the bits of a
-// binary64), and must hold every column's identity before the launch
-// (groupAggFill; the accumulators of MIN and MAX cannot be cleared by a
-// memset).  accAgg must be coarse-grained device memory (hipMalloc): the
-// floating-point atomics are hardware atomics only there.  One int64 column
-// with GROUP_SUM runs bpGroup itself; columns that are all int64 run the
-// integer-only kernels.  An LDS request above 160 KiB is refused.
-void groupAggFill(const GroupColumns &cols, unsigned long long *accAgg, uint64_t accSlots, hipStream_t s);
-void bpGroupAgg(const BPArgs &a, const BPItem *items, const uint32_t *nItems, uint32_t capacity,
-                const GroupColumns &cols, uint32_t *accCount, unsigned long long *accAgg, uint64_t accSlots,
-                hipStream_t s);
-// Rows (rid, count, agg_0, ..., agg_{C-1}) of unit u's positions, W = 2 + C
-// words each, otherwise as groupEmit (one column runs groupEmit itself).
-void groupEmitAgg(const BPArgs &a, const MarkUnit *units, const uint32_t *nUnits, uint32_t capacity,
-                  const uint32_t *accCount, const unsigned long long *accAgg, uint64_t accSlots, uint32_t columns,
-                  const unsigned long long *unitOffsets, unsigned long long *out, uint64_t outCapacity, hipStream_t s);
+               const uint32_t *accCount, const unsigned long long *accAgg, uint64_t accSlots, uint32_t columns,
+               const unsigned long long *unitOffsets, unsigned long long *out, uint64_t outCapacity, hipStream_t s);
 
 // Single-level counting join of unique inner keys (bitmap_join.hip): one
 // workgroup per network partition sets a 2^bits LDS bitmap from the inner

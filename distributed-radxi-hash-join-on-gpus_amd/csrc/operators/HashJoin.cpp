@@ -840,76 +840,43 @@ bool HashJoin::outputValid() const { return output && ctx->workspace().epoch() =
 bool HashJoin::outputRidsValid() const { return outputRids && ctx->workspace().epoch() == outputEpoch; }
 bool HashJoin::outputGroupsValid() const { return outputGroups && ctx->workspace().epoch() == outputEpoch; }
 
-void HashJoin::setGroupValues(const kernels::GroupValues &v) {
+void HashJoin::setGroupColumns(const kernels::GroupColumns &c, const char *who) {
   JOIN_ASSERT(plan.kind == core::JoinKind::Group, "HashJoin",
-              "a value column to sum (join_group) needs JoinConfig.kind = group, this join has kind = %s",
+              "value columns to aggregate (%s) need JoinConfig.kind = group, this join has kind = %s", who,
               core::joinKindName(plan.kind));
   JOIN_ASSERT(ctx->comm()->size() == 1, "HashJoin",
-              "join_group: a value column of a kind = group join needs a single rank (world size %u): the values of "
-              "outer tuples received from other ranks live on those ranks; without a value column every rank counts",
-              ctx->comm()->size());
-  JOIN_ASSERT(passes == 1, "HashJoin", "join_group: a value column cannot be combined with a capacity spill (%u passes)",
-              passes);
-  JOIN_ASSERT(v.values && v.strideWords >= 1, "HashJoin", "join_group: needs a value column with a positive stride");
-  JOIN_ASSERT(ridLo[1] > ridHi[1] || (ridLo[1] >= v.offset && ridHi[1] - v.offset < v.rows), "HashJoin",
-              "join_group: outer values [%lu, %lu) do not cover this rank's outer rids [%lu, %lu]",
-              (unsigned long)v.offset, (unsigned long)(v.offset + v.rows), (unsigned long)ridLo[1],
-              (unsigned long)ridHi[1]);
-  groupValues = v;
-  hasGroupValues = true;
-}
-
-JoinResult HashJoin::joinGroup(const uint64_t *outerValues, uint64_t outerOffset, uint64_t outerGlobal,
-                               uint64_t strideWords) {
-  kernels::GroupValues v;
-  v.values = outerValues;
-  v.offset = outerOffset;
-  v.rows = outerGlobal;
-  v.strideWords = strideWords;
-  setGroupValues(v);
-  struct Clear {
-    HashJoin &j;
-    ~Clear() { j.clearGroupValues(); }
-  } clear{*this};
-  return run();
-}
-
-void HashJoin::setGroupColumns(const kernels::GroupColumns &c) {
-  JOIN_ASSERT(plan.kind == core::JoinKind::Group, "HashJoin",
-              "value columns to aggregate (join_group_agg) need JoinConfig.kind = group, this join has kind = %s",
-              core::joinKindName(plan.kind));
-  JOIN_ASSERT(ctx->comm()->size() == 1, "HashJoin",
-              "join_group_agg: value columns of a kind = group join need a single rank (world size %u): the values of "
+              "%s: value columns of a kind = group join need a single rank (world size %u): the values of "
               "outer tuples received from other ranks live on those ranks; without value columns every rank counts",
-              ctx->comm()->size());
-  JOIN_ASSERT(passes == 1, "HashJoin",
-              "join_group_agg: value columns cannot be combined with a capacity spill (%u passes)", passes);
+              who, ctx->comm()->size());
+  JOIN_ASSERT(passes == 1, "HashJoin", "%s: value columns cannot be combined with a capacity spill (%u passes)", who,
+              passes);
   JOIN_ASSERT(c.n >= 1 && c.n <= kernels::GROUP_MAX_COLUMNS, "HashJoin",
-              "join_group_agg: %u value columns; a group join aggregates 1 to %u", c.n, kernels::GROUP_MAX_COLUMNS);
+              "%s: %u value columns; a group join aggregates 1 to %u", who, c.n, kernels::GROUP_MAX_COLUMNS);
   JOIN_ASSERT(c.n <= plan.groupColumns, "HashJoin",
-              "join_group_agg: %u value columns, but the plan sized its LDS tables for JoinConfig.groupColumns "
+              "%s: %u value columns, but the plan sized its LDS tables for JoinConfig.groupColumns "
               "(group_columns) = %u; set group_columns to the number of columns before constructing the join",
-              c.n, plan.groupColumns);
+              who, c.n, plan.groupColumns);
   for (uint32_t i = 0; i < c.n; ++i) {
-    JOIN_ASSERT(c.col[i] && c.stride[i] >= 1, "HashJoin", "join_group_agg: column %u needs values and a positive stride", i);
-    JOIN_ASSERT(c.agg[i] <= kernels::GROUP_MAX, "HashJoin", "join_group_agg: column %u has no aggregate %u", i, c.agg[i]);
+    JOIN_ASSERT(c.col[i] && c.stride[i] >= 1, "HashJoin", "%s: column %u needs values and a positive stride", who, i);
+    JOIN_ASSERT(c.agg[i] <= kernels::GROUP_MAX, "HashJoin", "%s: column %u has no aggregate %u", who, i, c.agg[i]);
     JOIN_ASSERT(c.dtype[i] <= kernels::GROUP_DTYPE_MAX, "HashJoin",
-                "join_group_agg: column %u has no element type %u (int64, int32, float64, float32)", i, c.dtype[i]);
+                "%s: column %u has no element type %u (int64, int32, float64, float32)", who, i, c.dtype[i]);
     JOIN_ASSERT(reinterpret_cast<uintptr_t>(c.col[i]) % kernels::groupDtypeBytes(c.dtype[i]) == 0, "HashJoin",
-                "join_group_agg: column %u (%s) is not aligned to its element size", i, kernels::groupDtypeName(c.dtype[i]));
+                "%s: column %u (%s) is not aligned to its element size", who, i, kernels::groupDtypeName(c.dtype[i]));
   }
   JOIN_ASSERT(ridLo[1] > ridHi[1] || (ridLo[1] >= c.offset && ridHi[1] - c.offset < c.rows), "HashJoin",
-              "join_group_agg: outer values [%lu, %lu) do not cover this rank's outer rids [%lu, %lu]",
+              "%s: outer values [%lu, %lu) do not cover this rank's outer rids [%lu, %lu]", who,
               (unsigned long)c.offset, (unsigned long)(c.offset + c.rows), (unsigned long)ridLo[1],
               (unsigned long)ridHi[1]);
   groupColumns = c;
   hasGroupColumns = true;
 }
 
-JoinResult HashJoin::joinGroupAgg(kernels::GroupColumns columns, uint64_t outerOffset, uint64_t outerGlobal) {
+JoinResult HashJoin::joinGroup(kernels::GroupColumns columns, uint64_t outerOffset, uint64_t outerGlobal,
+                               const char *who) {
   columns.offset = outerOffset;
   columns.rows = outerGlobal;
-  setGroupColumns(columns);
+  setGroupColumns(columns, who);
   struct Clear {
     HashJoin &j;
     ~Clear() { j.clearGroupColumns(); }
@@ -1075,20 +1042,7 @@ JoinResult HashJoin::runImpl() {
 
   // --------------------------------------------- local pass and build/probe
   LocalPhase local(env, localOverflowed, hasSink && (canFuseRows() || canFuseKindRows()) ? &sink : nullptr);
-  kernels::GroupValues oneSum;  // a single int64 SUM column takes the single-column kernels
-  if (hasGroupColumns && plan.kind == core::JoinKind::Group) {
-    if (groupColumns.n == 1 && groupColumns.agg[0] == kernels::GROUP_SUM && !kernels::groupColumnsTyped(groupColumns)) {
-      oneSum.values = static_cast<const uint64_t *>(groupColumns.col[0]);
-      oneSum.offset = groupColumns.offset;
-      oneSum.rows = groupColumns.rows;
-      oneSum.strideWords = groupColumns.stride[0];
-      local.setGroupValues(&oneSum);
-    } else {
-      local.setGroupColumns(&groupColumns);
-    }
-  } else if (hasGroupValues && plan.kind == core::JoinKind::Group) {
-    local.setGroupValues(&groupValues);
-  }
+  if (hasGroupColumns && plan.kind == core::JoinKind::Group) local.setGroupColumns(&groupColumns);
   local.run(run, result);
   const uint64_t t4 = nowUs();
   ctx->timeline().resolve();  // every stream was synchronised above

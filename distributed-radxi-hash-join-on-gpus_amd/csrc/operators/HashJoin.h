@@ -42,8 +42,7 @@ struct JoinResult {
   // matchedPairs the sum of their counts, unmatchedInner the rows with count 0.
   uint64_t matchedPairs = 0, unmatchedInner = 0, unmatchedOuter = 0;
   uint64_t outputGroups = 0;       // kind Group, materialize: rows written on this rank
-  bool groupSums = false;          // kind Group: the rows carry a sum (3 words, else 2)
-  uint32_t groupColumns = 0;       // kind Group: aggregate words per row (0 count only, 1 joinGroup; rows are 2 + this)
+  uint32_t groupColumns = 0;       // kind Group: aggregate words per row (0 count only; rows are 2 + this)
   bool rowsFused = false;          // materialize: whole rows went to the RowSink (no pair array)
   uint32_t reruns = 0;             // build/probe re-launches after an item/output overflow
   double joinMs = 0;               // host wall: histogram start -> local result available
@@ -114,24 +113,21 @@ class HashJoin {
   bool outputRidsValid() const;
   // kind Group with materialize: the rows of the last run()
   // (lastResult().outputGroups of them, any order; 2 + lastResult().groupColumns
-  // words: (rid, count), (rid, count, sum) or (rid, count, agg_0, ...)), in the engine's
-  // workspace under the same validity rule as getOutput().
+  // words: (rid, count, agg_0, ...)), in the engine's workspace under the
+  // same validity rule as getOutput().
   const uint64_t *getOutputGroups() const { return outputGroups; }
   bool outputGroupsValid() const;
-  // kind Group: while set, run() also sums the outer value column per group
-  // (N = 1: the values of other ranks' outer tuples are not here).  Throws
-  // unless the column covers this rank's outer rids.  joinGroup = set, run, clear.
-  void setGroupValues(const kernels::GroupValues &v);
-  void clearGroupValues() { hasGroupValues = false; }
-  JoinResult joinGroup(const uint64_t *outerValues, uint64_t outerOffset, uint64_t outerGlobal, uint64_t strideWords);
-  // kind Group: while set, run() aggregates cols.n (at most the plan's
+  // kind Group: while set, run() aggregates cols.n (1 ... the plan's
   // groupColumns) outer value columns per group, each by its own SUM, MIN or
-  // MAX; the rows are (rid, count, agg_0, ...).  The same checks as
-  // setGroupValues, for every column.  One SUM column runs as setGroupValues.
-  // joinGroupAgg = set (offset and rows from its arguments), run, clear.
-  void setGroupColumns(const kernels::GroupColumns &cols);
+  // MAX; the rows are (rid, count, agg_0, ...).  N = 1: the values of other
+  // ranks' outer tuples are not here.  Throws unless every column covers this
+  // rank's outer rids; `who` names the caller's entry point in the message
+  // (join_group, join_group_agg).  joinGroup = set (offset and rows from its
+  // arguments), run, clear.
+  void setGroupColumns(const kernels::GroupColumns &cols, const char *who);
   void clearGroupColumns() { hasGroupColumns = false; }
-  JoinResult joinGroupAgg(kernels::GroupColumns columns, uint64_t outerOffset, uint64_t outerGlobal);
+  JoinResult joinGroup(kernels::GroupColumns columns, uint64_t outerOffset, uint64_t outerGlobal,
+                       const char *who);
   // Fused materialization: while a sink is set, a device join at N = 1 over
   // the split layout writes whole output rows (LateMaterialization's layout)
   // from its materialize pass instead of pairs.  canFuseRows() says whether
@@ -218,8 +214,6 @@ class HashJoin {
   const ulonglong2 *output = nullptr;
   const uint64_t *outputRids = nullptr;
   const uint64_t *outputGroups = nullptr;
-  kernels::GroupValues groupValues;
-  bool hasGroupValues = false;
   kernels::GroupColumns groupColumns;
   bool hasGroupColumns = false;
   // Capacity spill (planPasses / runPasses): pass count, this rank's and the

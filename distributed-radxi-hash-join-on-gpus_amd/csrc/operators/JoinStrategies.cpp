@@ -197,7 +197,6 @@ bool ExactExchange::exchange(JoinRun &run) {
 tasks::BuildProbe *LocalPhase::addBuildProbe(data::Window *inner, data::Window *outer) {
   bps.emplace_back(new tasks::BuildProbe(inner, outer, env.ctx, env.plan, env.config.outputCapacity));
   if (sink) bps.back()->setRowSink(sink);
-  if (groupValues) bps.back()->setGroupValues(groupValues->values, groupValues->offset, groupValues->strideWords);
   if (groupColumns) bps.back()->setGroupColumns(groupColumns);
   if (env.config.outputHost && env.plan.materialize) {
     JOIN_ASSERT(env.config.outputCapacity > 0, "HashJoin", "outputHost needs outputCapacity (pairs it holds)");
@@ -294,8 +293,7 @@ void LocalPhase::run(JoinRun &run, JoinResult &r) {
   r.outputPairs = env.plan.materialize && !rids && !group && !bps.empty() ? bps.front()->getOutputCount() : 0;
   r.outputRids = env.plan.materialize && rids && !bps.empty() ? bps.front()->getOutputCount() : 0;
   r.outputGroups = env.plan.materialize && group && !bps.empty() ? bps.front()->getOutputCount() : 0;
-  r.groupSums = group && groupValues;
-  r.groupColumns = !group ? 0 : groupColumns ? groupColumns->n : groupValues ? 1 : 0;
+  r.groupColumns = group && groupColumns ? groupColumns->n : 0;
   if ((core::isOuterKind(env.plan.kind) || group) && !bps.empty()) {  // (never pipelined: one build/probe)
     r.matchedPairs = bps.front()->getMatchedPairs();
     r.unmatchedInner = bps.front()->getUnmatchedInner();

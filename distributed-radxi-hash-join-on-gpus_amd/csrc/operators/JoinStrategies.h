@@ -131,9 +131,7 @@ class LocalPhase {
   // Runs to completion (all streams synchronised); fills the counts of `r`.
   void run(JoinRun &run, JoinResult &r);
   std::vector<std::unique_ptr<tasks::BuildProbe>> &buildProbes() { return bps; }
-  // kind Group: the outer value column to sum (null: counts only).
-  void setGroupValues(const kernels::GroupValues *v) { groupValues = v; }
-  // kind Group: the outer value columns to aggregate (null: none).
+  // kind Group: the outer value columns to aggregate (null: counts only).
   void setGroupColumns(const kernels::GroupColumns *c) { groupColumns = c; }
   void release() {
     bps.clear();
@@ -145,7 +143,6 @@ class LocalPhase {
   JoinEnv &env;
   bool &localOverflowed;
   const kernels::RowSink *sink;  // fused row output (N = 1 materializing joins), or null
-  const kernels::GroupValues *groupValues = nullptr;
   const kernels::GroupColumns *groupColumns = nullptr;
   std::vector<std::unique_ptr<tasks::BuildProbe>> bps;
   std::vector<std::unique_ptr<data::Window>> outerViews;

@@ -365,21 +365,20 @@ void BuildProbe::executeOuter() {
 
 // Group join (kernels/group_join.hip): no pair is written and nothing can
 // overflow but the item list -- the rows are this rank's inner tuples.  The
-// accumulators (u32 counts, u64 sums over the positions of the partitioned
-// inner buffer) and the unit counts are zeroed here, so every re-run (item-list
-// overflow in collect(), the exact redo after a sampled local pass overflowed,
-// a second run()) starts clean.  With aggregated value columns (groupColumns)
-// there are C accumulators per position, column-major, and every run first
-// writes their identities (kernels::groupAggFill; the host twin does the same):
-// INT64_MAX and INT64_MIN are no memset pattern, nor are the +inf / -inf of a
-// float column (groupColumns carries each column's element type to the kernels
-// and the host twin).  The accumulators come from the Arena (hipMalloc,
-// coarse-grained), where the hardware float atomics of typed columns are valid.
+// accumulators (u32 counts and, column-major, C u64 aggregates per position of
+// the partitioned inner buffer; groupColumns carries each column's aggregate
+// and element type to the kernels and the host twin) and the unit counts are
+// reset here, so every re-run (item-list overflow in collect(), the exact redo
+// after a sampled local pass overflowed, a second run()) starts clean: the
+// counts are zeroed, the aggregates get their identities (kernels::groupAggInit;
+// the host twin writes them itself).  The accumulators come from the Arena
+// (hipMalloc, coarse-grained), where the hardware float atomics of typed
+// columns are valid.
 void BuildProbe::executeGroup() {
   const bool dev = ctx->onDevice();
-  const uint32_t C = groupColumns ? groupColumns->n : 0;
-  const bool sum = !C && groupValues != nullptr;
-  const uint64_t W = C ? 2 + C : sum ? 3 : 2;
+  const kernels::GroupColumns cols = groupColumns ? *groupColumns : kernels::GroupColumns();
+  const uint32_t C = cols.n;
+  const uint64_t W = 2 + C;
   memory::Arena &ws = ctx->workspace();
   performance::Timeline &tl = ctx->timeline();
   const double wb = (double)innerPartitionSize, wp = (double)outerPartitionSize;
@@ -388,25 +387,18 @@ void BuildProbe::executeGroup() {
   args.materialize = false;  // no pairs; plan.materialize asks for the rows
   const uint64_t slots = (windows[0]->getPartitionedCapacity() + 2) & ~1ull;  // (u32 counts zeroed as whole words)
   uint32_t *accCount = ws.getArray<uint32_t>(slots);
-  auto *accSum = sum || C ? ws.getArray<unsigned long long>(slots * std::max<uint32_t>(C, 1)) : nullptr;
+  auto *accAgg = C ? ws.getArray<unsigned long long>(slots * C) : nullptr;
   ctx->zero(accCount, slots * sizeof(uint32_t));
-  if (sum) ctx->zero(accSum, slots * sizeof(unsigned long long));
+  if (dev) kernels::groupAggInit(cols, accAgg, slots, ctx->stream());
   outputCapacity = innerPartitionSize;  // one row per inner tuple: cannot overflow
   outGroups = plan.materialize ? ws.getArray<uint64_t>(std::max<uint64_t>(1, outputCapacity * W)) : nullptr;
   if (!dev) {
     tl.begin("BPTASKTIME");
     tl.beginSplit("BPKERNEL", "BPBUILD", wb, "BPPROBE", wp);
     uint64_t rows = 0;
-    if (C) {
-      matchedPairs = host::buildProbeGroupAgg(args, *groupColumns, accCount, reinterpret_cast<uint64_t *>(accSum), slots);
-      unmatchedInner = host::groupEmitAgg(args, accCount, reinterpret_cast<const uint64_t *>(accSum), slots, C,
-                                          outGroups, outputCapacity, &rows);
-    } else {
-      matchedPairs = host::buildProbeGroup(args, groupValues, groupOffset, groupStride, accCount,
-                                           reinterpret_cast<uint64_t *>(accSum));
-      unmatchedInner = host::groupEmit(args, accCount, reinterpret_cast<const uint64_t *>(accSum), outGroups,
-                                       outputCapacity, &rows);
-    }
+    matchedPairs = host::buildProbeGroup(args, cols, accCount, reinterpret_cast<uint64_t *>(accAgg), slots);
+    unmatchedInner = host::groupEmit(args, accCount, reinterpret_cast<const uint64_t *>(accAgg), slots, C, outGroups,
+                                     outputCapacity, &rows);
     tl.end("BPKERNEL");
     tl.end("BPTASKTIME");
     unmatchedOuter = 0;
@@ -438,22 +430,17 @@ void BuildProbe::executeGroup() {
   performance::Measurements::add("BPMEMALLOC", (double)(performance::nowUs() - tAlloc), "us");
   performance::Measurements::add("BPMEMSIZE",
                                  (double)(2ull * P1 * 4 + kernels::scanWorkspaceBytes(std::max<uint64_t>(args.P, unitCapacityR)) +
-                                          (uint64_t)capacity * sizeof(kernels::BPItem) + slots * (4 + 8ull * (C ? C : sum)) +
+                                          (uint64_t)capacity * sizeof(kernels::BPItem) + slots * (4 + 8ull * C) +
                                           (uint64_t)unitCapacityR * (sizeof(kernels::MarkUnit) + 12) +
-                                          kernels::bpGroupLdsBytes(args, C ? C : sum)),
+                                          kernels::bpGroupLdsBytes(args, C)),
                                  "bytes");
   hipStream_t s = ctx->stream();
   kernels::bpPlanCounts(args, counts, s);
   kernels::scanExclusiveU32(counts, offsets, args.P, nItems, scanWs, s);
   kernels::bpEmit(args, counts, offsets, items, capacity, s);
   if (unitCounts) ctx->zero(unitCounts, (uint64_t)unitCapacityR * sizeof(uint32_t));
-  if (C) kernels::groupAggFill(*groupColumns, accSum, slots, s);
   tl.beginSplit("BPKERNEL", "BPBUILD", wb, "BPPROBE", wp, s);
-  if (C)
-    kernels::bpGroupAgg(args, items, nItems, capacity, *groupColumns, accCount, accSum, slots, s);
-  else
-    kernels::bpGroup(args, items, nItems, capacity, reinterpret_cast<const unsigned long long *>(groupValues), groupOffset,
-                     groupStride, accCount, accSum, s);  // -> counters[0], accumulators
+  kernels::bpGroup(args, items, nItems, capacity, cols, accCount, accAgg, slots, s);  // -> counters[0], accumulators
   // Inner units (counts / offsets are free again: bpEmit has consumed them in stream order).
   kernels::markPlanUnits(uargs, counts, s);
   kernels::scanExclusiveU32(counts, offsets, args.P, nUnits, scanWs, s);
@@ -462,12 +449,8 @@ void BuildProbe::executeGroup() {
     kernels::groupUnitLengths(uargs, units, nUnits, unitCapacityR, unitCounts, s);
     kernels::scanExclusiveU32to64(unitCounts, unitOffsets, unitCapacityR, counters + 1, scanWs, s);  // -> [1] rows
   }
-  if (C)
-    kernels::groupEmitAgg(uargs, units, nUnits, unitCapacityR, accCount, accSum, slots, C, unitOffsets,
-                          reinterpret_cast<unsigned long long *>(outGroups), outputCapacity, s);
-  else
-    kernels::groupEmit(uargs, units, nUnits, unitCapacityR, accCount, accSum, unitOffsets,
-                       reinterpret_cast<unsigned long long *>(outGroups), outputCapacity, s);  // -> counters[4], rows
+  kernels::groupEmit(uargs, units, nUnits, unitCapacityR, accCount, accAgg, slots, C, unitOffsets,
+                     reinterpret_cast<unsigned long long *>(outGroups), outputCapacity, s);  // -> counters[4], rows
   hipEvent_t done = tl.mark(s);
   tl.endAt("BPKERNEL", done);
   tl.endAt("BPTASKTIME", done);

@@ -11,11 +11,11 @@
 // the hit marks of the preserved sides) -> markCount(anti) over the units of
 // each preserved side -> (materialize) scans -> the inner join's place pass
 // -> markPlacePairs appends the NULL-padded rows (kernels/outer_join.hip).
-// Group joins: the same item list -> bpGroup (per-slot counters and sums in
-// LDS, added to accumulators over the inner positions) -> the inner side's
-// units -> (materialize) lengths, scan -> groupEmit writes the rows and counts
-// the empty groups (kernels/group_join.hip).  With aggregated value columns:
-// groupAggFill (the accumulators' identities) -> bpGroupAgg -> groupEmitAgg.
+// Group joins: the same item list -> groupAggInit (the accumulators'
+// identities) -> bpGroup (per-slot counters and aggregates in LDS, applied to
+// accumulators over the inner positions) -> the inner side's units ->
+// (materialize) lengths, scan -> groupEmit writes the rows and counts the
+// empty groups (kernels/group_join.hip).
 // With a row sink (HashJoin::setKindRowSink, device, N = 1) the place pass of
 // those kinds writes payload rows instead: markPlaceRows in place of markPlace
 // / markPlacePairs, and for outer kinds over the split layout the inner join's
@@ -66,19 +66,11 @@ class BuildProbe : public Task {
   const ulonglong2 *getOutput() const { return outPairs; }
   // kind != Inner, materialize: getOutputCount() outer rids (null otherwise).
   const uint64_t *getOutputRids() const { return outRids; }
-  // kind Group, materialize: getOutputCount() rows of 2 (rid, count) or, with
-  // a value column, 3 (rid, count, sum) or, with C aggregated columns, 2 + C
-  // words (null otherwise).
+  // kind Group, materialize: getOutputCount() rows (rid, count, agg_0, ...) of
+  // 2 + C words for C aggregated columns (null otherwise).
   const uint64_t *getOutputGroups() const { return outGroups; }
-  // kind Group: sum values[(rid - offset) * strideWords] over each group's
-  // outer tuples (the column covers this rank's outer rids; null = counts only).
-  void setGroupValues(const uint64_t *values, uint64_t offset, uint64_t strideWords) {
-    groupValues = values;
-    groupOffset = offset;
-    groupStride = strideWords;
-  }
-  // kind Group: aggregate cols.n value columns instead (kernels::GroupColumns; null = none).  The rows are
-  // then (rid, count, agg_0, ...): 2 + cols.n words.
+  // kind Group: aggregate cols.n outer value columns per group (kernels::GroupColumns; the columns cover this
+  // rank's outer rids; null = counts only).  The rows are then (rid, count, agg_0, ...): 2 + cols.n words.
   void setGroupColumns(const kernels::GroupColumns *cols) { groupColumns = cols; }
   bool outputOverflowed() const { return overflowOut; }
   // Fused row output (device, split layout): the materialize pass writes whole
@@ -123,9 +115,7 @@ class BuildProbe : public Task {
   ulonglong2 *outPairs = nullptr;
   uint64_t *outRids = nullptr;               // semi / anti: outer rid list (workspace)
   uint64_t *outGroups = nullptr;             // group: rows (workspace)
-  const uint64_t *groupValues = nullptr;     // group: outer value column (null = counts only)
-  uint64_t groupOffset = 0, groupStride = 1;
-  const kernels::GroupColumns *groupColumns = nullptr;  // group: aggregated value columns (null = none)
+  const kernels::GroupColumns *groupColumns = nullptr;  // group: aggregated value columns (null = counts only)
   uint32_t unitCapacity = 0;                 // semi / anti / outer kinds: upper bound of the outer units
   uint32_t unitCapacityR = 0;                // outer kinds preserving R: upper bound of the inner units
   uint64_t matchedPairs = 0, unmatchedInner = 0, unmatchedOuter = 0;  // outer kinds (matches = their sum)
