@@ -383,6 +383,78 @@ bool runFaultCase(uint32_t ranks, uint64_t G) {
   return ok;
 }
 
+// Key-column relations on the host path: every rank holds a slice of two key
+// columns (rids = global positions) and the materializing join of the
+// expansions must give the pairs of the tuple relations built from the same
+// keys and rids.  The expansion is allocated, filled and freed under the
+// sanitizers.
+bool runKeyColumnCase(uint32_t ranks, uint64_t G) {
+  std::vector<uint64_t> keys[2];
+  for (int s = 0; s < 2; ++s) {
+    keys[s].resize(G);
+    for (uint64_t i = 0; i < G; ++i) keys[s][i] = kernels::mix64(i * 2 + s + 7) % (G / 2 + 1);
+  }
+  auto group = std::make_shared<comm::InProcessGroup>(ranks);
+  std::vector<std::vector<std::pair<uint64_t, uint64_t>>> got(2 * ranks);
+  std::vector<int> failed(ranks, 0);
+  auto rankMain = [&](uint32_t r) {
+    try {
+      comm::InProcessCommunicator comm(group, r);
+      core::ExecContext ctx(Location::Host, -1, &comm);
+      core::JoinConfig cfg;
+      cfg.materialize = true;
+      cfg.outputCapacity = 8 * G;  // keys repeat on both sides: about two pairs per outer tuple, on whichever rank
+      const uint64_t off = data::Relation::localOffsetFor(G, r, ranks), n = data::Relation::localSizeFor(G, r, ranks);
+      for (int columns = 1; columns >= 0; --columns) {
+        std::unique_ptr<data::Relation> rel[2];
+        for (int s = 0; s < 2; ++s) {
+          if (columns) {
+            rel[s].reset(new data::Relation(keys[s].data() + off, n, G, Location::Host, 0, off));
+          } else {
+            rel[s].reset(new data::Relation(n, G, Location::Host, 0));
+            for (uint64_t i = 0; i < n; ++i) rel[s]->getData()[i] = data::Tuple{keys[s][off + i], off + i};
+          }
+        }
+        operators::HashJoin j(rel[0].get(), rel[1].get(), &ctx, cfg);
+        const operators::JoinResult res = j.run();
+        const auto want = columns ? operators::JoinResult::Expanded : operators::JoinResult::Tuples;
+        if (res.keyColumns[0] != want || res.keyColumns[1] != want || rel[0]->expanded() != (columns == 1) ||
+            res.outputOverflow)
+          failed[r] = 1;
+        const ulonglong2 *out = j.getOutput();
+        for (uint64_t i = 0; i < res.outputPairs; ++i) got[2 * r + columns].emplace_back(out[i].x, out[i].y);
+      }
+    } catch (const std::exception &e) {
+      std::printf("[key_columns] rank %u: %s\n", r, e.what());
+      failed[r] = 1;
+    }
+  };
+  std::vector<std::thread> ts;
+  for (uint32_t r = 0; r < ranks; ++r) ts.emplace_back(rankMain, r);
+  for (auto &t : ts) t.join();
+  bool ok = true;
+  std::vector<std::pair<uint64_t, uint64_t>> all[2];
+  for (uint32_t r = 0; r < ranks; ++r) {
+    ok = ok && !failed[r];
+    for (int c = 0; c < 2; ++c) all[c].insert(all[c].end(), got[2 * r + c].begin(), got[2 * r + c].end());
+  }
+  for (auto &a : all) std::sort(a.begin(), a.end());
+  uint64_t expected = 0;
+  {
+    std::unordered_map<uint64_t, uint64_t> copies;
+    for (uint64_t k : keys[0]) ++copies[k];
+    for (uint64_t k : keys[1]) {
+      auto it = copies.find(k);
+      if (it != copies.end()) expected += it->second;
+    }
+  }
+  ok = ok && all[0] == all[1] && all[1].size() == expected;
+  for (const auto &p : all[1]) ok = ok && p.first < G && p.second < G && keys[0][p.first] == keys[1][p.second];
+  std::printf("[key_columns] ranks=%u pairs=%lu expected=%lu %s\n", ranks, (unsigned long)all[1].size(),
+              (unsigned long)expected, ok ? "OK" : "FAIL");
+  return ok;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -432,6 +504,7 @@ int main(int argc, char **argv) {
   };
   bool ok = true;
   for (const Case &c : cases) ok = runCase(c, ranks, G) && ok;
+  ok = runKeyColumnCase(ranks, G) && ok;
   ok = runFaultCase(ranks, G) && ok;
   std::printf("%s\n", ok ? "ALL OK" : "FAILED");
   return ok ? 0 : 1;

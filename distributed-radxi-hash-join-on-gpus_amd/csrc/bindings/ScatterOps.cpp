@@ -70,12 +70,17 @@ py::dict opNetScatterSlices(const at::Tensor &tuples, int64_t bits, const std::s
                             int64_t keyBits, int64_t mixBits, int64_t narrowArg, int64_t maxBlocks,
                             int64_t sampleStride, int64_t roundLpArg, int64_t dLo, int64_t range, int64_t shrink,
                             int64_t guard, bool unbounded) {
-  TORCH_CHECK(tuples.is_cuda() && tuples.dim() == 2 && tuples.size(1) == 2 && tuples.scalar_type() == at::kLong &&
-                  tuples.is_contiguous(),
-              "net_scatter_slices: tuples must be a contiguous device int64 tensor of shape [n, 2] (key, rid)");
+  // [n, 2] (key, rid) tuples, or a 1-D key column for the formats that write no rid.
+  const bool column = tuples.dim() == 1;
   const bool compressed = format == "compressed", keyOnly = format == "key_only", frag = format == "frag",
              wide = format == "wide", packed = format == "frag_packed";
   TORCH_CHECK(compressed || keyOnly || frag || wide || packed, "net_scatter_slices: format ", format);
+  TORCH_CHECK(!column || !(compressed || wide), "net_scatter_slices: format ", format,
+              " carries a rid, which a 1-D key column does not have; key columns take frag, frag_packed and key_only");
+  TORCH_CHECK(tuples.is_cuda() && (column || (tuples.dim() == 2 && tuples.size(1) == 2)) &&
+                  tuples.scalar_type() == at::kLong && tuples.is_contiguous(),
+              "net_scatter_slices: tuples must be a contiguous device int64 tensor of shape [n, 2] (key, rid), or [n] "
+              "(a key column)");
   // Packed fragment words (kernels.h, PK_*): the window and the slice tables count u64 words.
   TORCH_CHECK(!packed || (bits <= kernels::PK_MAX_PART_BITS && !unbounded && shrink % kernels::PK_CHUNK_WORDS == 0 &&
                           (roundLpArg == 0 || roundLpArg >= 3)),
@@ -96,7 +101,8 @@ py::dict opNetScatterSlices(const at::Tensor &tuples, int64_t bits, const std::s
   const uint32_t F = 1u << bits, G = CLAIM_GROUPS;
   const uint32_t Fp = range ? (uint32_t)range : F;  // slices per group
   const kernels::KeyMix mix{mixBits ? 1u : 0u, mixBits ? (uint32_t)mixBits : 64u};
-  const data::Tuple *in = ptr<const data::Tuple>(tuples);
+  const kernels::KeySource in = column ? kernels::KeySource::column(ptr<const uint64_t>(tuples))
+                                       : kernels::KeySource(ptr<const data::Tuple>(tuples));
 
   // sidePlan(): geometry, stride, scale, window capacity.
   const auto geom = kernels::partitionGeometry(n, (uint32_t)maxBlocks);
@@ -194,8 +200,8 @@ py::dict opNetScatterSlices(const at::Tensor &tuples, int64_t bits, const std::s
     kernels::netScatterFrag(in, n, (uint32_t)bits, geom, 0, geom.blocks, gcur, ptr<uint32_t>(window), st,
                             (uint32_t)keyBits, mix, gend, nm, roundMeta);
   else if (wide)
-    kernels::netScatterWide(in, n, (uint32_t)bits, geom, 0, geom.blocks, gcur, ptr<data::Tuple>(window), st, mix, gend,
-                            nm);
+    kernels::netScatterWide(ptr<const data::Tuple>(tuples), n, (uint32_t)bits, geom, 0, geom.blocks, gcur,
+                            ptr<data::Tuple>(window), st, mix, gend, nm);
   else
     kernels::netScatter(in, n, (uint32_t)bits, keyOnly ? 0u : (uint32_t)keyShift, geom, 0, geom.blocks, gcur,
                         ptr<uint64_t>(window), st, (uint32_t)keyBits, mix, gend, nm, !keyOnly, roundMeta);
@@ -441,7 +447,8 @@ void bindScatterOps(py::module_ &ops) {
           py::arg("max_blocks") = 2048, py::arg("sample_stride") = 1, py::arg("round_lp") = 0, py::arg("d_lo") = 0,
           py::arg("range") = 0, py::arg("shrink") = 0, py::arg("guard") = 0, py::arg("unbounded") = false,
           "The sampled network pass of one relation (layout + bounded claim scatter) into a sentinel-filled window; "
-          "format = compressed | key_only | frag | wide | frag_packed (window and slice tables in packed u64 words)");
+          "format = compressed | key_only | frag | wide | frag_packed (window and slice tables in packed u64 words); "
+          "tuples may be a 1-D key column for the formats without a rid (key_only, frag, frag_packed)");
   ops.def("local_scatter_slices", &opLocalScatterSlices, py::arg("window"), py::arg("runs"), py::arg("owned"),
           py::arg("shift"), py::arg("bits"), py::arg("mode"), py::arg("round_map") = std::make_tuple(0, 0, 0),
           py::arg("frag_shift") = 32, py::arg("lo_shift") = 0, py::arg("narrow") = -1, py::arg("sample_stride") = 1,

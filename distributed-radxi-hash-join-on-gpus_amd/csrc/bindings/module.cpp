@@ -105,7 +105,14 @@ std::tuple<at::Tensor, at::Tensor> opNetPartition(const at::Tensor &tuples, int6
 }
 
 at::Tensor opNetHistogram(const at::Tensor &tuples, int64_t bits, int64_t maxBlocks) {
-  checkTuples(tuples, "tuples");
+  const bool column = tuples.dim() == 1;  // a key column: the device kernel reads it in place
+  if (column) {
+    TORCH_CHECK(tuples.scalar_type() == at::kLong && tuples.is_contiguous(),
+                "net_histogram: a key column must be a contiguous 1-D int64 tensor");
+    if (!tuples.is_cuda()) return opNetHistogram(at::stack({tuples, at::zeros_like(tuples)}, 1), bits, maxBlocks);
+  } else {
+    checkTuples(tuples, "tuples");
+  }
   setDevice(tuples);
   const uint64_t n = tuples.size(0);
   const uint32_t F = 1u << bits;
@@ -113,7 +120,9 @@ at::Tensor opNetHistogram(const at::Tensor &tuples, int64_t bits, int64_t maxBlo
   at::Tensor blockHist = at::empty({(int64_t)F * g.blocks}, like(tuples, at::kInt));
   at::Tensor totals = at::empty({(int64_t)F}, like(tuples));
   if (tuples.is_cuda()) {
-    kernels::netHistogram(ptr<data::Tuple>(tuples), n, bits, g, ptr<uint32_t>(blockHist), nullptr);
+    const kernels::KeySource in = column ? kernels::KeySource::column(ptr<const uint64_t>(tuples))
+                                         : kernels::KeySource(ptr<const data::Tuple>(tuples));
+    kernels::netHistogram(in, n, bits, g, ptr<uint32_t>(blockHist), nullptr);
     kernels::digitTotals(ptr<uint32_t>(blockHist), F, g.blocks, g.blocks, 1, ptr<uint64_t>(totals), nullptr);
     HIP_CHECK(hipDeviceSynchronize());
   } else {
@@ -1484,6 +1493,8 @@ py::dict resultToDict(const operators::JoinResult &r) {
   d["build_probe_items"] = r.buildProbeItems;
   d["inner_local"] = r.innerLocal;
   d["outer_local"] = r.outerLocal;
+  d["key_columns"] = py::make_tuple(operators::JoinResult::keyColumnUseName(r.keyColumns[0]),
+                                    operators::JoinResult::keyColumnUseName(r.keyColumns[1]));
   return d;
 }
 
@@ -1977,6 +1988,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
             return r;
           },
           py::arg("tuples"), py::arg("global_size"))
+      .def_static(
+          "from_keys",
+          [](at::Tensor keys, uint64_t globalSize, uint64_t ridOffset) {
+            // A plain key column, read in place: the rid of keys[i] is rid_offset + i.
+            std::ostringstream shape;
+            shape << keys.sizes();
+            TORCH_CHECK(keys.scalar_type() == at::kLong && keys.dim() == 1 && keys.is_contiguous(),
+                        "Relation.from_keys: keys must be a contiguous 1-D int64 tensor, got dtype ",
+                        keys.scalar_type(), " with shape ", shape.str(),
+                        keys.is_contiguous() ? "" : " (not contiguous)");
+            if (keys.is_cuda()) HIP_CHECK(hipDeviceSynchronize());
+            PyRelation r;
+            r.rel = std::make_shared<data::Relation>(reinterpret_cast<const uint64_t *>(keys.data_ptr()),
+                                                     (uint64_t)keys.size(0), globalSize, locOf(keys),
+                                                     keys.is_cuda() ? keys.get_device() : 0, ridOffset);
+            r.keepAlive = py::cast(keys);
+            return r;
+          },
+          py::arg("keys"), py::arg("global_size"), py::arg("rid_offset") = 0)
+      .def_property_readonly("is_key_column", [](PyRelation &r) { return r.rel->isKeyColumn(); })
+      .def_property_readonly("expanded", [](PyRelation &r) { return r.rel->expanded(); },
+                             "A key column whose {key, rid} tuples have been built (something asked for them)")
       .def("local_size", [](PyRelation &r) { return r.rel->getLocalSize(); })
       .def("global_size", [](PyRelation &r) { return r.rel->getGlobalSize(); })
       .def("location", [](PyRelation &r) { return std::string(locationName(r.rel->location())); })

@@ -22,7 +22,7 @@ std::string JoinConfig::describe() const {
 std::string JoinPlan::describe() const {
   return utils::format("JoinPlan(nodes=%u networkBits=%u localBits=%u twoLevel=%d keyShift=%u fragShift=%u "
                        "rChunk=%u sChunk=%u chunks=%u wide=%d materialize=%d keyMix=%d sampled=%d assignment=%s wire=%u/%u "
-                       "split=%d splitHist=%d pipeOuter=%d bitmap=%d/%u%s%s%s%s%s%s%s%s%s%s)",
+                       "split=%d splitHist=%d pipeOuter=%d bitmap=%d/%u%s%s%s%s%s%s%s%s%s%s%s%s)",
                        numberOfNodes, networkBits, localBits, (int)twoLevel, keyShift, fragShift, rChunk, sChunk,
                        chunks, (int)wide, (int)materialize, (int)keyMix, (int)sampledNetwork,
                        assignment == AssignmentPolicy::LPT ? "lpt" : "round_robin", wireBits[0], wireBits[1],
@@ -32,7 +32,13 @@ std::string JoinPlan::describe() const {
                        oneSided ? " oneSided" : "", fragments && !bitmapJoin ? " fragments" : "",
                        innerRepeats ? " innerRepeats" : "", kind == JoinKind::Inner ? "" : " kind=",
                        kind == JoinKind::Inner ? "" : joinKindName(kind),
-                       kind == JoinKind::Group ? utils::format(" groupColumns=%u", groupColumns).c_str() : "");
+                       kind == JoinKind::Group ? utils::format(" groupColumns=%u", groupColumns).c_str() : "",
+                       // Key-column sides, and whether this plan's network pass reads them in place.
+                       keyColumn[0] && keyColumn[1] ? " keyColumns=inner,outer"
+                       : keyColumn[0]               ? " keyColumns=inner"
+                       : keyColumn[1]               ? " keyColumns=outer"
+                                                    : "",
+                       !(keyColumn[0] || keyColumn[1]) ? "" : readsKeyColumns() ? "(in place)" : "(expanded)");
 }
 
 JoinPlan makePlan(const JoinConfig &cfg, uint32_t numberOfNodes, uint64_t globalInner, uint64_t globalOuter,

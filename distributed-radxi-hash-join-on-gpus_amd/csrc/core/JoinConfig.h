@@ -258,6 +258,23 @@ struct JoinPlan {
   // fragments), the bitmap plans and the pipelined outer side.
   // (The set bitmap plan of a count-only semi / anti join is rid-free too.)
   bool carriesRids() const { return materialize || (kind != JoinKind::Inner && !bitmapSet); }
+  // Sides given as key columns (data::Relation::isKeyColumn), inner then outer.
+  // The network pass of one device rank (singleDeviceRank, set by HashJoin)
+  // reads them in place when its scatter writes no rid (readsKeyColumns): the
+  // bitmap plan's fragment scatters, sampled or exact; key-only words, sampled
+  // or exact (so also after a slice overflow made the join exact); and u32
+  // fragments of the two-level plan, which only the sampled pass writes -- the
+  // exact pass of that plan (networkExact: after a slice overflow) writes
+  // CompressedTuples with rids.  Everything else -- rid-carrying scatters,
+  // N > 1, the host path, key-hash spill passes -- asks the relation for
+  // tuples and so for its expansion.
+  bool keyColumn[2] = {false, false};
+  bool singleDeviceRank = false;
+  bool networkExact = false;  // a sampled slice overflowed: this and later joins run the exact network pass
+  bool readsKeyColumns() const {
+    if (!singleDeviceRank || carriesRids() || wide) return false;
+    return bitmapJoin || keyOnly || (fragments && sampledNetwork && !networkExact);
+  }
   bool keyMix = false;        // radix digits from kernels::KeyMix{keyBits} of the key
   // Counting join whose keys do not fit a CompressedTuple (sparse 63-bit keys):
   // after the network pass a tuple is the 8-byte word key >> networkBits (no

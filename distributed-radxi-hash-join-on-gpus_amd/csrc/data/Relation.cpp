@@ -30,14 +30,37 @@ Relation::Relation(Tuple *external, uint64_t localSize, uint64_t globalSize, Loc
     : localSize(localSize), globalSize(globalSize), data(external), loc_(loc), device_(device), owns_(false),
       fromPool_(false) {}
 
+Relation::Relation(const uint64_t *keys, uint64_t localSize, uint64_t globalSize, Location loc, int device,
+                   uint64_t ridBase)
+    : localSize(localSize), globalSize(globalSize), data(nullptr), loc_(loc), device_(device), owns_(false),
+      fromPool_(false), keyColumn_(true), keys_(keys) {
+  JOIN_ASSERT(keys || localSize == 0, "Relation", "key column of %lu keys without memory", (unsigned long)localSize);
+  ridsPositional_ = true;
+  ridBase_ = ridBase;
+}
+
 Relation::~Relation() {
   // Pool memory is released by Pool::freeAll (the reference freed it here).
-  if (owns_ && !fromPool_) memory::Arena::rawFree(loc_, data);
+  if (owns_ && !fromPool_ && data) memory::Arena::rawFree(loc_, data);
 }
 
 uint64_t Relation::getLocalSize() { return localSize; }
 uint64_t Relation::getGlobalSize() { return globalSize; }
-Tuple *Relation::getData() { return data; }
+
+Tuple *Relation::getData() {
+  if (keyColumn_ && !data) {  // the expansion: built once, owned from here on
+    data = static_cast<Tuple *>(memory::Arena::rawAlloc(loc_, std::max<uint64_t>(localSize, 1) * sizeof(Tuple), device_));
+    owns_ = true;
+    if (loc_ == Location::Device) {
+      HIP_CHECK(hipSetDevice(device_));
+      kernels::expandKeys(keys_, localSize, ridBase_, data, nullptr);
+      HIP_CHECK(hipDeviceSynchronize());
+    } else {
+      for (uint64_t i = 0; i < localSize; ++i) data[i] = Tuple{keys_[i], ridBase_ + i};
+    }
+  }
+  return data;
+}
 
 uint64_t Relation::localSizeFor(uint64_t globalSize, uint32_t nodeId, uint32_t numberOfNodes) {
   // Same split as /root/reference/main.cpp:73-79: the last rank takes the remainder.
@@ -59,7 +82,15 @@ static void runGenerate(Tuple *out, uint64_t n, const kernels::GenParams &p, Loc
   }
 }
 
+// Generators and distribute() rewrite the tuples in place: a key column is a
+// read-only view of the caller's keys and has none to rewrite.
+void Relation::requireTuples(const char *what) const {
+  JOIN_ASSERT(!keyColumn_, "Relation", "%s: this relation is a view of a caller's key column (from_keys) and cannot be "
+              "rewritten; generate into a tuple relation instead", what);
+}
+
 void Relation::fillUniqueValues(uint64_t startKeyValue, uint64_t startRidValue) {
+  requireTuples("fillUniqueValues");
   kernels::GenParams p;
   p.dist = KeyDistribution::Unique;
   p.globalOffset = 0;
@@ -74,6 +105,7 @@ void Relation::fillUniqueValues(uint64_t startKeyValue, uint64_t startRidValue) 
 }
 
 void Relation::fillModuloValues(uint64_t startKeyValue, uint64_t startRidValue, uint64_t innerRelationSize) {
+  requireTuples("fillModuloValues");
   JOIN_ASSERT(innerRelationSize > 0, "Relation", "modulo size must be > 0");
   kernels::GenParams p;
   p.dist = KeyDistribution::Modulo;
@@ -89,6 +121,7 @@ void Relation::fillModuloValues(uint64_t startKeyValue, uint64_t startRidValue, 
 }
 
 void Relation::generate(const GenSpec &spec, uint64_t globalOffset) {
+  requireTuples("generate");
   kernels::GenParams p;
   p.dist = spec.distribution;
   p.globalOffset = globalOffset;
@@ -179,6 +212,7 @@ void Relation::randomOrder() {
 void Relation::distribute(uint32_t nodeId, uint32_t numberOfNodes, comm::Communicator *comm) {
   // Reference (Relation.cpp:99-141): pairwise swap of sections, then reshuffle.
   // Here: section k of every rank goes to rank k in one all-to-all.
+  requireTuples("distribute");
   if (numberOfNodes <= 1) return;
   JOIN_ASSERT(loc_ != Location::Pinned, "Relation", "distribute() of a pinned host relation is not supported");
   JOIN_ASSERT(comm && comm->size() == numberOfNodes && comm->rank() == nodeId, "Relation",
@@ -217,10 +251,11 @@ void Relation::distribute(uint32_t nodeId, uint32_t numberOfNodes, comm::Communi
 void Relation::debugKeyPrint(uint64_t limit) {
   const uint64_t n = std::min(limit, localSize);
   std::vector<Tuple> h(n);
+  const Tuple *tuples = getData();  // a key column: its expansion
   if (deviceAccessible(loc_))
-    HIP_CHECK(hipMemcpy(h.data(), data, n * sizeof(Tuple), hipMemcpyDefault));
+    HIP_CHECK(hipMemcpy(h.data(), tuples, n * sizeof(Tuple), hipMemcpyDefault));
   else
-    std::memcpy(h.data(), data, n * sizeof(Tuple));
+    std::memcpy(h.data(), tuples, n * sizeof(Tuple));
   for (uint64_t i = 0; i < n; ++i) std::fprintf(stdout, "%lu, ", (unsigned long)h[i].key);
   std::fprintf(stdout, "\n");
   std::fflush(stdout);

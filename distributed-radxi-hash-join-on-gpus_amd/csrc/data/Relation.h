@@ -41,13 +41,27 @@ class Relation {
   Relation(uint64_t localSize, uint64_t globalSize, Location loc, int device = 0);
   // Non-owning view of caller memory (e.g. a torch tensor).
   Relation(Tuple *external, uint64_t localSize, uint64_t globalSize, Location loc, int device = 0);
+  // Non-owning view of a caller's key column: local tuple i is {keys[i],
+  // ridBase + i}.  Rids are positional and the key bound unknown, as for any
+  // external data.  Kernels that never read a rid take the column in place
+  // (keySource()); everything else sees tuples through getData(), which builds
+  // them once into a buffer this relation owns (the expansion).
+  Relation(const uint64_t *keys, uint64_t localSize, uint64_t globalSize, Location loc, int device, uint64_t ridBase);
   ~Relation();
   Relation(const Relation &) = delete;
   Relation &operator=(const Relation &) = delete;
 
   uint64_t getLocalSize();
   uint64_t getGlobalSize();
-  Tuple *getData();
+  Tuple *getData();  // a key column: its expansion, built on the first call
+  bool isKeyColumn() const { return keyColumn_; }
+  const uint64_t *keys() const { return keys_; }
+  bool expanded() const { return keyColumn_ && data != nullptr; }
+  // The keys for kernels that read nothing else: the column itself (no
+  // expansion is made), or the tuples of any other relation.
+  kernels::KeySource keySource() {
+    return keyColumn_ ? kernels::KeySource::column(keys_) : kernels::KeySource(data);
+  }
   Location location() const { return loc_; }
   int device() const { return device_; }
 
@@ -94,6 +108,7 @@ class Relation {
   void randomOrder();
   void ensureHostMirror();
   void setGenerated(uint64_t ridBase, bool lowBitsUniform);
+  void requireTuples(const char *what) const;
 
  protected:
   uint64_t localSize;
@@ -105,6 +120,8 @@ class Relation {
   int device_;
   bool owns_;
   bool fromPool_;
+  bool keyColumn_ = false;
+  const uint64_t *keys_ = nullptr;
   uint64_t maxKey_ = 0;
   bool keyBoundKnown_ = false;
   bool ridsPositional_ = false;

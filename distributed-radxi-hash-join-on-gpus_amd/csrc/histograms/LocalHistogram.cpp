@@ -51,7 +51,8 @@ void LocalHistogram::computeLocalHistogram() {
   blockHist = ctx->workspace().getArray<uint32_t>((uint64_t)F * geom.blocks);
   if (ctx->onDevice()) {
     totalsDev = ctx->workspace().getArray<uint64_t>((uint64_t)chunks * F);
-    kernels::netHistogram(relation->getData(), relation->getLocalSize(), bits, geom, blockHist, ctx->stream(), mix);
+    // (The device histogram reads keys only: a key column in place, whatever the scatter will need.)
+    kernels::netHistogram(relation->keySource(), relation->getLocalSize(), bits, geom, blockHist, ctx->stream(), mix);
     kernels::digitTotals(blockHist, F, geom.blocks, bpc, chunks, totalsDev, ctx->stream());
     ctx->copy(chunkValues.data(), totalsDev, chunkValues.size() * 8, false, true);
   } else {
@@ -66,7 +67,7 @@ void LocalHistogram::computeLocalHistogramDevice() {
   summed = false;
   blockHist = ctx->workspace().getArray<uint32_t>((uint64_t)F * geom.blocks);
   totalsDev = ctx->workspace().getArray<uint64_t>((uint64_t)chunks * F);
-  kernels::netHistogram(relation->getData(), relation->getLocalSize(), bits, geom, blockHist, ctx->stream(), mix);
+  kernels::netHistogram(relation->keySource(), relation->getLocalSize(), bits, geom, blockHist, ctx->stream(), mix);
   kernels::digitTotals(blockHist, F, geom.blocks, bpc, chunks, totalsDev, ctx->stream());
 }
 
@@ -78,7 +79,7 @@ void LocalHistogram::computeSampledEstimate(uint32_t stride) {
   uint32_t *sampleHist = ctx->workspace().getArray<uint32_t>((uint64_t)F * geom.blocks);
   if (ctx->onDevice()) {
     uint64_t *t = ctx->workspace().getArray<uint64_t>((uint64_t)chunks * F);
-    kernels::netHistogram(relation->getData(), relation->getLocalSize(), bits, geom, sampleHist, ctx->stream(), mix,
+    kernels::netHistogram(relation->keySource(), relation->getLocalSize(), bits, geom, sampleHist, ctx->stream(), mix,
                           std::max<uint32_t>(1, stride));
     kernels::digitTotals(sampleHist, F, geom.blocks, bpc, chunks, t, ctx->stream());
     ctx->copy(chunkValues.data(), t, chunkValues.size() * 8, false, true);

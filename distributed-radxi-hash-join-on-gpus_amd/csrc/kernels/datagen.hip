@@ -85,6 +85,22 @@ void generate(data::Tuple *out, uint64_t n, const GenParams &p, hipStream_t s) {
   HIP_CHECK_LAUNCH();
 }
 
+// The tuples of a key column (data::Relation's expansion): {keys[i], ridBase + i}.
+__global__ __launch_bounds__(256) void expandKeysKernel(const uint64_t *__restrict__ keys, uint64_t n, uint64_t ridBase,
+                                                        ulonglong2 *__restrict__ out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    out[i] = make_ulonglong2(keys[i], ridBase + i);
+}
+
+void expandKeys(const uint64_t *keys, uint64_t n, uint64_t ridBase, data::Tuple *out, hipStream_t s) {
+  if (n == 0) return;
+  const uint64_t want = ceilDiv(n, 256);
+  hipLaunchKernelGGL(expandKeysKernel, dim3((uint32_t)(want < 8192 ? want : 8192)), dim3(256), 0, s, keys, n, ridBase,
+                     reinterpret_cast<ulonglong2 *>(out));
+  HIP_CHECK_LAUNCH();
+}
+
 // Loads this file's code object at engine start (kernels::preloadCodeObjects).
 void preloadDatagen() {
   hipFuncAttributes a;

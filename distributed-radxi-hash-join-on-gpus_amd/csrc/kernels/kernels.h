@@ -63,6 +63,8 @@ struct GenParams {
 };
 HJ_HD uint64_t tpchSparseKey(uint64_t k) { return (k >> 3) * 32 + (k & 7) + 1; }
 void generate(data::Tuple *out, uint64_t n, const GenParams &p, hipStream_t s);
+// out[i] = {keys[i], ridBase + i}: the tuples of a key column (data::Relation::getData).
+void expandKeys(const uint64_t *keys, uint64_t n, uint64_t ridBase, data::Tuple *out, hipStream_t s);
 // Oracle of skewed joins: counts[key - lo] += 1 for keys in [lo, lo + domain)
 // (u32 counts, zeroed by the caller); *outside += keys outside that range.
 void countKeys(const data::Tuple *in, uint64_t n, uint64_t lo, uint64_t domain, uint32_t *counts,
@@ -101,8 +103,32 @@ HJ_HD uint64_t sparseKey(uint64_t k) {
   return m.apply((k ^ 0x2545F4914F6CDD1DULL) & SPARSE_KEY_MAX);
 }
 
+// Where a kernel that never reads a rid finds its keys: key i is the 8-byte
+// word base[i * strideWords].  strideWords = 2: 16-byte {key, rid} tuples (any
+// tuple pointer converts); 1: a plain key column, read in place -- half the
+// input bytes, and a wave's loads are contiguous.  Entry points that carry
+// rids refuse a column (the rid of element i would be its position).
+struct KeySource {
+  const uint64_t *base = nullptr;
+  uint32_t strideWords = 2;
+  KeySource() = default;
+  KeySource(const data::Tuple *tuples) : base(reinterpret_cast<const uint64_t *>(tuples)), strideWords(2) {}
+  static KeySource column(const uint64_t *keys) {
+    KeySource k;
+    k.base = keys;
+    k.strideWords = 1;
+    return k;
+  }
+  bool isColumn() const { return strideWords == 1; }
+  KeySource operator+(uint64_t i) const {
+    KeySource k = *this;
+    k.base += i * strideWords;
+    return k;
+  }
+};
+
 // blockHist is digit-major [F][blocks] (u32).
-void netHistogram(const data::Tuple *in, uint64_t n, uint32_t bits, const PartitionGeometry &g,
+void netHistogram(KeySource in, uint64_t n, uint32_t bits, const PartitionGeometry &g,
                   uint32_t *blockHist, hipStream_t s, KeyMix mix = KeyMix(), uint32_t sampleStride = 1);
 // Sampled variant (sampleStride > 1): every workgroup counts only tiles 0, S,
 // 2S, ... of its own range (estimates for the single-rank sampled network pass).
@@ -115,11 +141,12 @@ void netGroupTotals(const uint32_t *blockHist, uint32_t F, uint32_t blocks, uint
 uint32_t sampleStrideFor(const PartitionGeometry &g, uint64_t n, uint32_t F, uint32_t stride);
 // Sampled [NGROUPS][F] totals: every sampleStride-th tile of each XCD group
 // (the tile set sampleScale() counts as seen); totals are cleared first.
-void netSampledTotals(const data::Tuple *in, uint64_t n, uint32_t bits, const PartitionGeometry &g,
+void netSampledTotals(KeySource in, uint64_t n, uint32_t bits, const PartitionGeometry &g,
                       uint64_t *totals, hipStream_t s, KeyMix mix, uint32_t sampleStride);
-// Both sides of a join in one launch (one clear when the totals are adjacent).
+// Both sides of a join in one launch (one clear when the totals are adjacent);
+// either side may be a key column.
 struct SampledInput {
-  const data::Tuple *data;
+  KeySource data;
   uint64_t n;
   PartitionGeometry geom;
   uint32_t stride;
@@ -176,8 +203,9 @@ void netGroupCursors(const uint32_t *blockHist, uint32_t F, uint32_t blocks, uin
 // keyBits: bits of the largest key (lets the kernel carry the digit in the
 // packed word's spare top bits instead of a separate LDS array).
 // withRids = false: key-only words (value = mixed key >> bits, keyShift 0) for
-// counting joins whose keys do not fit a CompressedTuple (JoinPlan::keyOnly).
-void netScatter(const data::Tuple *in, uint64_t n, uint32_t bits, uint32_t keyShift, const PartitionGeometry &g,
+// counting joins whose keys do not fit a CompressedTuple (JoinPlan::keyOnly);
+// only these read a key column.
+void netScatter(KeySource in, uint64_t n, uint32_t bits, uint32_t keyShift, const PartitionGeometry &g,
                 uint32_t blockBegin, uint32_t blockEnd, void *gcur, uint64_t *out, hipStream_t s,
                 uint32_t keyBits = 64, KeyMix mix = KeyMix(), const void *gend = nullptr, int narrowMode = -1,
                 bool withRids = true, const uint32_t *roundMeta = nullptr);
@@ -190,7 +218,7 @@ void netScatterWide(const data::Tuple *in, uint64_t n, uint32_t bits, const Part
 // keyBits <= 32 the digit rides in the staged word, above that (e.g. 6B dense
 // keys, 33 bits) the tile keeps a separate digit array.
 HJ_HD bool fragWordFits(uint32_t keyBits, uint32_t bits) { return keyBits <= 32 + bits; }
-void netScatterFrag(const data::Tuple *in, uint64_t n, uint32_t bits, const PartitionGeometry &g, uint32_t blockBegin,
+void netScatterFrag(KeySource in, uint64_t n, uint32_t bits, const PartitionGeometry &g, uint32_t blockBegin,
                     uint32_t blockEnd, void *gcur, uint32_t *out, hipStream_t s, uint32_t keyBits,
                     KeyMix mix = KeyMix(), const void *gend = nullptr, int narrowMode = -1,
                     const uint32_t *roundMeta = nullptr);
@@ -224,7 +252,7 @@ HJ_HD uint64_t packFragments(uint32_t f0, uint32_t f1, uint32_t f2, uint32_t cou
 // fragment (mixed key >> bits) wider than 20 bits is stored saturated and adds
 // 1 to *wideFlag (BitmapCounters::dup: the join falls back as for a fragment
 // outside the planned range).
-void netScatterFragPacked(const data::Tuple *in, uint64_t n, uint32_t bits, const PartitionGeometry &g, void *gcur,
+void netScatterFragPacked(KeySource in, uint64_t n, uint32_t bits, const PartitionGeometry &g, void *gcur,
                           uint64_t *out, hipStream_t s, KeyMix mix, const void *gend, bool narrow,
                           const uint32_t *roundMeta, unsigned long long *wideFlag);
 // Partition-group pass of the same scatter: only tuples whose digit is in
@@ -232,7 +260,7 @@ void netScatterFragPacked(const data::Tuple *in, uint64_t n, uint32_t bits, cons
 // gend laid out by netSampledLayout with the same range); the others are read
 // and dropped.  range < 1024 (one sentinel counter in the tile's LDS arrays).
 // The final claim cursors count every kept tuple (overflow check as usual).
-void netScatterFragRange(const data::Tuple *in, uint64_t n, uint32_t bits, const PartitionGeometry &g, void *gcur,
+void netScatterFragRange(KeySource in, uint64_t n, uint32_t bits, const PartitionGeometry &g, void *gcur,
                          uint32_t *out, hipStream_t s, uint32_t keyBits, KeyMix mix, const void *gend, bool narrow,
                          uint32_t dLo, uint32_t range);
 // Sampled network pass sized on the device (no host round trip): from the
@@ -964,7 +992,7 @@ void npjProbePairs(const data::Tuple *S, uint64_t nS, const unsigned long long *
 // in[0, n) into a set in ws (sampleRepeatsBytes(S)); *repeats = sampled keys
 // that were already in it.
 size_t sampleRepeatsBytes(uint32_t S);
-void sampleRepeats(const data::Tuple *in, uint64_t n, uint32_t S, void *ws, unsigned int *repeats, hipStream_t s);
+void sampleRepeats(KeySource in, uint64_t n, uint32_t S, void *ws, unsigned int *repeats, hipStream_t s);
 // Stream-mix ceiling (microbench.hip): n elements, read streams of ra / rb
 // bytes, write streams of wa / wb bytes per element (0 = none), in order.
 void streamMix(int ra, int rb, int wa, int wb, const void *a, const void *b, void *oa, void *ob, uint64_t n,
@@ -987,8 +1015,9 @@ void gatherVariant(int mode, const uint64_t *rids, uint64_t n, const ulonglong2 
 namespace hpcjoin {
 namespace kernels {
 // out[0] = max key, out[1] = max rid, out[2] = min rid over n tuples (device);
-// out[0..1] must be zeroed and out[2] set to ~0.
-void keyRidMax(const data::Tuple *in, uint64_t n, unsigned long long *out, hipStream_t s);
+// out[0..1] must be zeroed and out[2] set to ~0.  A key column gives the key
+// maximum only: its rids are positions, whose bounds the caller knows.
+void keyRidMax(KeySource in, uint64_t n, unsigned long long *out, hipStream_t s);
 }  // namespace kernels
 }  // namespace hpcjoin
 

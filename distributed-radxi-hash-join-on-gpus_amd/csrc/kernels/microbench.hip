@@ -227,17 +227,33 @@ __global__ __launch_bounds__(256) void keyRidMaxKernel(const ulonglong2 *__restr
   }
 }
 
+// The same over a key column: out[0] = max key; out[1..2] are left alone.
+__global__ __launch_bounds__(256) void keyMaxKernel(const unsigned long long *__restrict__ in, uint64_t n,
+                                                    unsigned long long *out) {
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  unsigned long long k = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) k = in[i] > k ? in[i] : k;
+#pragma unroll
+  for (int o = WAVE / 2; o > 0; o >>= 1) {
+    const unsigned long long k2 = __shfl_xor(k, o, WAVE);
+    k = k2 > k ? k2 : k;
+  }
+  if ((threadIdx.x & (WAVE - 1)) == 0) atomicMax(&out[0], k);
+}
+
 // Plan-time duplicate probe of the inner keys (HashJoin::makeJoinPlan, for
 // relations whose generator did not say): S keys at evenly spaced positions
 // go into a global open-addressing set of 2^tbits >= 2S entries (CAS); a key
 // that finds itself already there counts one repeat.  ~0 (the empty marker)
 // is skipped.  One launch, no sort, ~20 us for 64K samples.
-__global__ __launch_bounds__(256) void sampleRepeatsKernel(const ulonglong2 *__restrict__ in, uint64_t n, uint32_t S,
+// (sw: words between keys, KeySource::strideWords.)
+__global__ __launch_bounds__(256) void sampleRepeatsKernel(const unsigned long long *__restrict__ in, uint32_t sw,
+                                                           uint64_t n, uint32_t S,
                                                            unsigned long long *__restrict__ set, uint32_t tbits,
                                                            unsigned int *__restrict__ repeats) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= S) return;
-  const unsigned long long key = in[(uint64_t)((unsigned __int128)i * n / S)].x;
+  const unsigned long long key = in[(uint64_t)((unsigned __int128)i * n / S) * sw];
   if (key == ~0ull) return;
   const uint32_t mask = (1u << tbits) - 1;
   uint32_t h = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - tbits));
@@ -254,22 +270,26 @@ __global__ __launch_bounds__(256) void sampleRepeatsKernel(const ulonglong2 *__r
 
 size_t sampleRepeatsBytes(uint32_t S) { return ((size_t)8 << ceilLog2(2ull * std::max<uint32_t>(S, 1))) + 16; }
 
-void sampleRepeats(const data::Tuple *in, uint64_t n, uint32_t S, void *ws, unsigned int *repeats, hipStream_t s) {
+void sampleRepeats(KeySource in, uint64_t n, uint32_t S, void *ws, unsigned int *repeats, hipStream_t s) {
   if (n == 0 || S == 0) return;
   const uint32_t tbits = ceilLog2(2ull * S);
   auto *set = static_cast<unsigned long long *>(ws);
   HIP_CHECK(hipMemsetAsync(set, 0xFF, (size_t)8 << tbits, s));
   HIP_CHECK(hipMemsetAsync(repeats, 0, sizeof(unsigned int), s));
   hipLaunchKernelGGL(sampleRepeatsKernel, dim3(ceilDiv(S, 256)), dim3(256), 0, s,
-                     reinterpret_cast<const ulonglong2 *>(in), n, S, set, tbits, repeats);
+                     reinterpret_cast<const unsigned long long *>(in.base), in.strideWords, n, S, set, tbits, repeats);
   HIP_CHECK_LAUNCH();
 }
 
-void keyRidMax(const data::Tuple *in, uint64_t n, unsigned long long *out, hipStream_t s) {
+void keyRidMax(KeySource in, uint64_t n, unsigned long long *out, hipStream_t s) {
   if (n == 0) return;
   const uint32_t blocks = (uint32_t)std::min<uint64_t>(ceilDiv(n, 256), 2048);
-  hipLaunchKernelGGL(keyRidMaxKernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const ulonglong2 *>(in), n,
-                     out);
+  if (in.isColumn())
+    hipLaunchKernelGGL(keyMaxKernel, dim3(blocks), dim3(256), 0, s,
+                       reinterpret_cast<const unsigned long long *>(in.base), n, out);
+  else
+    hipLaunchKernelGGL(keyRidMaxKernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const ulonglong2 *>(in.base),
+                       n, out);
   HIP_CHECK_LAUNCH();
 }
 

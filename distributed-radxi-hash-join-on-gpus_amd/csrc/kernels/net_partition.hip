@@ -31,8 +31,22 @@ PartitionGeometry partitionGeometry(uint64_t n, uint32_t maxBlocks) {
   return g;
 }
 
+// Calls fn with the typed element pointer of a key source: 16-byte tuples or
+// a key column (kernels.h, KeySource).
+template <class Fn>
+static void withKeyElements(const char *who, const KeySource &in, Fn &&fn) {
+  HJ_CHECK(in.strideWords == 1 || in.strideWords == 2, "%s: keys %u words apart", who, in.strideWords);
+  if (in.isColumn())
+    fn(reinterpret_cast<const uint64_t *>(in.base));
+  else
+    fn(reinterpret_cast<const ulonglong2 *>(in.base));
+}
+__device__ __forceinline__ uint64_t keyOf(const ulonglong2 &x) { return x.x; }
+__device__ __forceinline__ uint64_t keyOf(const uint64_t &x) { return x; }
+
 // ------------------------------------------------------- histogram (pass 1)
-__device__ __forceinline__ void netHistogramBody(const ulonglong2 *__restrict__ in, uint64_t n, uint32_t tpb,
+template <typename InT>
+__device__ __forceinline__ void netHistogramBody(const InT *__restrict__ in, uint64_t n, uint32_t tpb,
                                                  uint32_t bits, uint32_t *__restrict__ blockHist, KeyMix mix,
                                                  uint32_t stride, uint32_t *hsh) {
   const uint32_t F = 1u << bits, mask = F - 1;
@@ -47,7 +61,7 @@ __device__ __forceinline__ void netHistogramBody(const ulonglong2 *__restrict__ 
 #pragma unroll
     for (int i = 0; i < (int)PART_ITEMS; ++i) {
       const uint64_t idx = base + (uint64_t)i * NT + threadIdx.x;
-      k[i] = idx < end ? mix.apply(in[idx].x) : 0;
+      k[i] = idx < end ? mix.apply(keyOf(in[idx])) : 0;
     }
 #pragma unroll
     for (int i = 0; i < (int)PART_ITEMS; ++i) {
@@ -62,33 +76,36 @@ __device__ __forceinline__ void netHistogramBody(const ulonglong2 *__restrict__ 
 
 // Exact (every tile) and sampled (1 tile in `stride`) launches are separate
 // kernels so that a trace tells a full pre-read from a sample.
-__global__ __launch_bounds__(NT) void netHistogramKernel(const ulonglong2 *__restrict__ in, uint64_t n,
-                                                         uint32_t tpb, uint32_t bits,
-                                                         uint32_t *__restrict__ blockHist, KeyMix mix) {
+template <typename InT>
+__global__ __launch_bounds__(NT) void netHistogramKernel(const InT *__restrict__ in, uint64_t n, uint32_t tpb,
+                                                         uint32_t bits, uint32_t *__restrict__ blockHist,
+                                                         KeyMix mix) {
   extern __shared__ __attribute__((aligned(16))) uint32_t hsh[];
   netHistogramBody(in, n, tpb, bits, blockHist, mix, 1, hsh);
 }
 
-__global__ __launch_bounds__(NT) void netSampledHistogramKernel(const ulonglong2 *__restrict__ in, uint64_t n,
-                                                                uint32_t tpb, uint32_t bits,
-                                                                uint32_t *__restrict__ blockHist, KeyMix mix,
-                                                                uint32_t stride) {
+template <typename InT>
+__global__ __launch_bounds__(NT) void netSampledHistogramKernel(const InT *__restrict__ in, uint64_t n, uint32_t tpb,
+                                                                uint32_t bits, uint32_t *__restrict__ blockHist,
+                                                                KeyMix mix, uint32_t stride) {
   extern __shared__ __attribute__((aligned(16))) uint32_t hsh[];
   netHistogramBody(in, n, tpb, bits, blockHist, mix, stride, hsh);
 }
 
-void netHistogram(const data::Tuple *in, uint64_t n, uint32_t bits, const PartitionGeometry &g,
-                  uint32_t *blockHist, hipStream_t s, KeyMix mix, uint32_t sampleStride) {
+void netHistogram(KeySource in, uint64_t n, uint32_t bits, const PartitionGeometry &g, uint32_t *blockHist,
+                  hipStream_t s, KeyMix mix, uint32_t sampleStride) {
   HJ_CHECK(bits >= 1 && bits <= MAX_PART_BITS, "netHistogram: bits=%u out of range", bits);
   HJ_CHECK(sampleStride >= 1, "netHistogram: sampleStride must be >= 1");
   const size_t lds = size_t(4) << bits << 2;
-  if (sampleStride > 1)
-    hipLaunchKernelGGL(netSampledHistogramKernel, dim3(g.blocks), dim3(NT), lds, s,
-                       reinterpret_cast<const ulonglong2 *>(in), n, g.tilesPerBlock, bits, blockHist, mix,
-                       sampleStride);
-  else
-    hipLaunchKernelGGL(netHistogramKernel, dim3(g.blocks), dim3(NT), lds, s, reinterpret_cast<const ulonglong2 *>(in),
-                       n, g.tilesPerBlock, bits, blockHist, mix);
+  withKeyElements("netHistogram", in, [&](auto *src) {
+    using InT = std::remove_cv_t<std::remove_pointer_t<decltype(src)>>;
+    if (sampleStride > 1)
+      hipLaunchKernelGGL(netSampledHistogramKernel<InT>, dim3(g.blocks), dim3(NT), lds, s, src, n, g.tilesPerBlock,
+                         bits, blockHist, mix, sampleStride);
+    else
+      hipLaunchKernelGGL(netHistogramKernel<InT>, dim3(g.blocks), dim3(NT), lds, s, src, n, g.tilesPerBlock, bits,
+                         blockHist, mix);
+  });
   HIP_CHECK_LAUNCH();
 }
 
@@ -108,7 +125,8 @@ __host__ __device__ inline uint64_t sampledTile(uint64_t local, uint32_t g, uint
 }
 
 struct SampledSideArgs {
-  const ulonglong2 *in;
+  const uint64_t *in;  // key i at in[i << wordShift]: 1 = tuples, 0 = a key column
+  uint32_t wordShift;
   uint64_t n;
   uint32_t tpb, blocks, stride;
   unsigned long long *totals;  // [NGROUPS][F]
@@ -128,8 +146,8 @@ __global__ __launch_bounds__(NT) void netSampledTotalsKernel(SampledSideArgs a, 
   const uint64_t begin = tile * PART_TILE, n = sd.n;
   if (tile / sd.tpb >= sd.blocks || begin >= n) return;  // uniform over the workgroup
   const uint64_t end = min(n, begin + PART_TILE);
-  const ulonglong2 *__restrict__ in = sd.in;
-  const uint32_t F = 1u << bits, mask = F - 1;
+  const uint64_t *__restrict__ in = sd.in;
+  const uint32_t F = 1u << bits, mask = F - 1, ws = sd.wordShift;
   for (uint32_t i = threadIdx.x; i < 4 * F; i += NT) hsh[i] = 0;
   __syncthreads();
   uint32_t *wh = hsh + (threadIdx.x / WAVE) * F;
@@ -137,7 +155,7 @@ __global__ __launch_bounds__(NT) void netSampledTotalsKernel(SampledSideArgs a, 
 #pragma unroll
   for (int i = 0; i < (int)PART_ITEMS; ++i) {
     const uint64_t idx = begin + (uint64_t)i * NT + threadIdx.x;
-    k[i] = idx < end ? mix.apply(in[idx].x) : 0;
+    k[i] = idx < end ? mix.apply(in[idx << ws]) : 0;
   }
 #pragma unroll
   for (int i = 0; i < (int)PART_ITEMS; ++i) {
@@ -183,7 +201,9 @@ static uint32_t sampledWorkgroups(const PartitionGeometry &g, uint64_t n, uint32
 
 static SampledSideArgs sampledSide(const SampledInput &x) {
   HJ_CHECK(x.stride >= 1, "netSampledTotals: sampleStride must be >= 1");
-  return SampledSideArgs{reinterpret_cast<const ulonglong2 *>(x.data), x.n, x.geom.tilesPerBlock, x.geom.blocks,
+  HJ_CHECK(x.data.strideWords == 1 || x.data.strideWords == 2, "netSampledTotals: keys %u words apart",
+           x.data.strideWords);
+  return SampledSideArgs{x.data.base, x.data.strideWords - 1, x.n, x.geom.tilesPerBlock, x.geom.blocks,
                          x.stride, reinterpret_cast<unsigned long long *>(x.totals)};
 }
 
@@ -210,7 +230,7 @@ void netSampledTotals(const SampledInput *sides, uint32_t count, uint32_t bits, 
   HIP_CHECK_LAUNCH();
 }
 
-void netSampledTotals(const data::Tuple *in, uint64_t n, uint32_t bits, const PartitionGeometry &g,
+void netSampledTotals(KeySource in, uint64_t n, uint32_t bits, const PartitionGeometry &g,
                       uint64_t *totals, hipStream_t s, KeyMix mix, uint32_t sampleStride) {
   const SampledInput one{in, n, g, sampleStride, totals};
   netSampledTotals(&one, 1, bits, s, mix);
@@ -380,12 +400,12 @@ static bool digitFitsOnTop(uint32_t bits, uint32_t keyShift, uint32_t keyBits) {
 // Only 1024 x 8 compiles without scratch for every policy.
 // digits: claim slices per group (filtered range passes); else 2^bits.
 template <class Pol>
-static void launchNetClaim(const Pol &pol, const data::Tuple *in, uint64_t n, uint32_t bits,
+static void launchNetClaim(const Pol &pol, const void *in, uint64_t n, uint32_t bits,
                            const PartitionGeometry &g, uint32_t blockBegin, uint32_t blockEnd, void *gcur,
                            void *out, hipStream_t s, const void *gend, bool narrow,
                            const uint32_t *roundMeta = nullptr, uint32_t digits = 0) {
   const uint32_t F = digits ? digits : 1u << bits;
-  const auto *src = reinterpret_cast<const typename Pol::InT *>(in);
+  const auto *src = static_cast<const typename Pol::InT *>(in);
   auto *dst = reinterpret_cast<typename Pol::OutT *>(out);
   const dim3 grid(blockEnd - blockBegin);
   auto go = [&](auto cur, auto maxd) {
@@ -446,45 +466,50 @@ static void setDigits(Pol &pol, uint32_t bits, KeyMix mix) {
 
 // Calls fn with the fragment policy of kb-bit (mixed) keys: the digit rides on
 // top of the staged u32 when fragment + digit fit it, else in the tile's digit array.
-template <bool FILT, class Fn>
+// In: the input element (ulonglong2 tuples or a uint64_t key column).
+template <bool FILT, typename In, class Fn>
 static void withFragPol(uint32_t kb, KeyMix mix, Fn &&fn) {
   const bool digitOnTop = kb <= 32;
   if (mix.on && digitOnTop)
-    fn(NetFragPolT<true, FILT>());
+    fn(NetFragPolT<true, FILT, In>());
   else if (digitOnTop)
-    fn(NetFragPolT<false, FILT>());
+    fn(NetFragPolT<false, FILT, In>());
   else if (mix.on)
-    fn(NetFragDigPolT<true, FILT>());
+    fn(NetFragDigPolT<true, FILT, In>());
   else
-    fn(NetFragDigPolT<false, FILT>());
+    fn(NetFragDigPolT<false, FILT, In>());
 }
 
-void netScatter(const data::Tuple *in, uint64_t n, uint32_t bits, uint32_t keyShift, const PartitionGeometry &g,
+void netScatter(KeySource in, uint64_t n, uint32_t bits, uint32_t keyShift, const PartitionGeometry &g,
                 uint32_t blockBegin, uint32_t blockEnd, void *gcur, uint64_t *out, hipStream_t s, uint32_t keyBits,
                 KeyMix mix, const void *gend, int narrowMode, bool withRids, const uint32_t *roundMeta) {
   const bool narrow = narrowMode < 0 ? cursorsNarrow(n) : narrowMode != 0;
   if (!netScatterArgs("netScatter", n, bits, g, blockBegin, blockEnd)) return;
   HJ_CHECK(withRids || keyShift == 0, "netScatter: key-only words need keyShift 0 (got %u)", keyShift);
   if (!withRids) {  // key >> bits always leaves `bits` spare top bits
-    auto go = [&](auto kpol) {
-      setDigits(kpol, bits, mix);
-      launchNetClaim(kpol, in, n, bits, g, blockBegin, blockEnd, gcur, out, s, gend, narrow, roundMeta);
-    };
-    if (mix.on)
-      go(NetKeyPol<true>());
-    else
-      go(NetKeyPol<false>());
+    withKeyElements("netScatter", in, [&](auto *src) {
+      using In = std::remove_cv_t<std::remove_pointer_t<decltype(src)>>;
+      auto go = [&](auto kpol) {
+        setDigits(kpol, bits, mix);
+        launchNetClaim(kpol, src, n, bits, g, blockBegin, blockEnd, gcur, out, s, gend, narrow, roundMeta);
+      };
+      if (mix.on)
+        go(NetKeyPol<true, In>());
+      else
+        go(NetKeyPol<false, In>());
+    });
     return;
   }
+  HJ_CHECK(!in.isColumn(), "netScatter: CompressedTuples carry a rid; a key column has none to read");
   NetCompressedPol pol;
   setDigits(pol, bits, mix);
   pol.keyShift = keyShift;
   if (digitFitsOnTop(bits, keyShift, mix.on ? std::max(keyBits, mix.bits) : keyBits)) {
-    launchNetClaim(pol, in, n, bits, g, blockBegin, blockEnd, gcur, out, s, gend, narrow, roundMeta);
+    launchNetClaim(pol, in.base, n, bits, g, blockBegin, blockEnd, gcur, out, s, gend, narrow, roundMeta);
   } else {
     NetCompressedDigPol dpol;
     static_cast<NetCompressedPol &>(dpol) = pol;
-    launchNetClaim(dpol, in, n, bits, g, blockBegin, blockEnd, gcur, out, s, gend, narrow, roundMeta);
+    launchNetClaim(dpol, in.base, n, bits, g, blockBegin, blockEnd, gcur, out, s, gend, narrow, roundMeta);
   }
 }
 
@@ -498,7 +523,7 @@ void netScatterWide(const data::Tuple *in, uint64_t n, uint32_t bits, const Part
   launchNetClaim(pol, in, n, bits, g, blockBegin, blockEnd, gcur, out, s, gend, narrow);
 }
 
-void netScatterFrag(const data::Tuple *in, uint64_t n, uint32_t bits, const PartitionGeometry &g, uint32_t blockBegin,
+void netScatterFrag(KeySource in, uint64_t n, uint32_t bits, const PartitionGeometry &g, uint32_t blockBegin,
                     uint32_t blockEnd, void *gcur, uint32_t *out, hipStream_t s, uint32_t keyBits, KeyMix mix,
                     const void *gend, int narrowMode, const uint32_t *roundMeta) {
   const bool narrow = narrowMode < 0 ? cursorsNarrow(n) : narrowMode != 0;
@@ -507,13 +532,16 @@ void netScatterFrag(const data::Tuple *in, uint64_t n, uint32_t bits, const Part
   HJ_CHECK(fragWordFits(kb, bits), "netScatterFrag: %u-bit keys leave a fragment wider than %u bits above %u radix bits",
            kb, 32 - bits, bits);
   if (!any) return;
-  withFragPol<false>(kb, mix, [&](auto pol) {
-    setDigits(pol, bits, mix);
-    launchNetClaim(pol, in, n, bits, g, blockBegin, blockEnd, gcur, out, s, gend, narrow, roundMeta);
+  withKeyElements("netScatterFrag", in, [&](auto *src) {
+    using In = std::remove_cv_t<std::remove_pointer_t<decltype(src)>>;
+    withFragPol<false, In>(kb, mix, [&](auto pol) {
+      setDigits(pol, bits, mix);
+      launchNetClaim(pol, src, n, bits, g, blockBegin, blockEnd, gcur, out, s, gend, narrow, roundMeta);
+    });
   });
 }
 
-void netScatterFragPacked(const data::Tuple *in, uint64_t n, uint32_t bits, const PartitionGeometry &g, void *gcur,
+void netScatterFragPacked(KeySource in, uint64_t n, uint32_t bits, const PartitionGeometry &g, void *gcur,
                           uint64_t *out, hipStream_t s, KeyMix mix, const void *gend, bool narrow,
                           const uint32_t *roundMeta, unsigned long long *wideFlag) {
   const bool any = netScatterArgs("netScatterFragPacked", n, bits, g, 0, g.blocks);
@@ -522,16 +550,18 @@ void netScatterFragPacked(const data::Tuple *in, uint64_t n, uint32_t bits, cons
   HJ_CHECK(gend && wideFlag, "netScatterFragPacked: bounded slices and a flag word are required");
   if (!any) return;
   const uint32_t F = 1u << bits;
-  const auto *src = reinterpret_cast<const ulonglong2 *>(in);
   auto *dst = reinterpret_cast<unsigned long long *>(out);
   auto go = [&](auto mixed, auto cur) {
     using C = decltype(cur);
     constexpr bool MIX = decltype(mixed)::value;
     constexpr size_t lds = packedScatterLds<C>();
     static_assert(lds <= 160 * 1024, "packed scatter: LDS carve exceeds a CU");
-    hipLaunchKernelGGL((netScatterFragPackedKernel<MIX, C>), dim3(g.blocks), dim3(CL_NTH), lds, s, src, n,
-                       g.tilesPerBlock, F, bits, mix, reinterpret_cast<C *>(gcur), dst,
-                       reinterpret_cast<const C *>(gend), roundMeta, wideFlag);
+    withKeyElements("netScatterFragPacked", in, [&](auto *src) {
+      using In = std::remove_cv_t<std::remove_pointer_t<decltype(src)>>;
+      hipLaunchKernelGGL((netScatterFragPackedKernel<MIX, C, In>), dim3(g.blocks), dim3(CL_NTH), lds, s, src, n,
+                         g.tilesPerBlock, F, bits, mix, reinterpret_cast<C *>(gcur), dst,
+                         reinterpret_cast<const C *>(gend), roundMeta, wideFlag);
+    });
   };
   auto width = [&](auto mixed) {
     if (narrow)
@@ -546,7 +576,7 @@ void netScatterFragPacked(const data::Tuple *in, uint64_t n, uint32_t bits, cons
   HIP_CHECK_LAUNCH();
 }
 
-void netScatterFragRange(const data::Tuple *in, uint64_t n, uint32_t bits, const PartitionGeometry &g, void *gcur,
+void netScatterFragRange(KeySource in, uint64_t n, uint32_t bits, const PartitionGeometry &g, void *gcur,
                          uint32_t *out, hipStream_t s, uint32_t keyBits, KeyMix mix, const void *gend, bool narrow,
                          uint32_t dLo, uint32_t range) {
   const bool any = netScatterArgs("netScatterFragRange", n, bits, g, 0, g.blocks);
@@ -557,11 +587,14 @@ void netScatterFragRange(const data::Tuple *in, uint64_t n, uint32_t bits, const
            "netScatterFragRange: digits [%u, %u) of %u (at most %u per pass, bounded slices)", dLo, dLo + range,
            1u << bits, padDigits(1) - 1);
   if (!any) return;
-  withFragPol<true>(kb, mix, [&](auto pol) {
-    setDigits(pol, bits, mix);
-    pol.dLo = dLo;
-    pol.range = range;
-    launchNetClaim(pol, in, n, bits, g, 0, g.blocks, gcur, out, s, gend, narrow, nullptr, range);
+  withKeyElements("netScatterFragRange", in, [&](auto *src) {
+    using In = std::remove_cv_t<std::remove_pointer_t<decltype(src)>>;
+    withFragPol<true, In>(kb, mix, [&](auto pol) {
+      setDigits(pol, bits, mix);
+      pol.dLo = dLo;
+      pol.range = range;
+      launchNetClaim(pol, src, n, bits, g, 0, g.blocks, gcur, out, s, gend, narrow, nullptr, range);
+    });
   });
 }
 
@@ -795,7 +828,7 @@ uint64_t sampledLayoutCapacityBound(const SampleScale &sc, uint32_t F) {
 // Loads this file's code object at engine start (kernels::preloadCodeObjects).
 void preloadNetPartition() {
   hipFuncAttributes a;
-  HIP_CHECK(hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&netHistogramKernel)));
+  HIP_CHECK(hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&netHistogramKernel<ulonglong2>)));
   HIP_CHECK(hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&netScatterFragPackedKernel<false, uint32_t>)));
 }
 

@@ -58,9 +58,13 @@ struct PlainLoad {
   using LoadT = In;
   static __device__ __forceinline__ LoadT load(const In *p) { return Loader<In>::load(p); }
 };
+// In = uint64_t: the input is a key column (kernels.h, KeySource), the same
+// 8-byte load from elements 8 bytes apart: a wave's load instruction then
+// covers 512 contiguous bytes instead of every other 8 of 1024.
+template <typename In = ulonglong2>
 struct KeyLoad {
   using LoadT = uint64_t;
-  static __device__ __forceinline__ LoadT load(const ulonglong2 *p) {
+  static __device__ __forceinline__ LoadT load(const In *p) {
     return __builtin_nontemporal_load(reinterpret_cast<const uint64_t *>(p));
   }
 };
@@ -111,9 +115,10 @@ __device__ __forceinline__ uint64_t mixKey(const KeyMix &m, uint64_t k) {
   else
     return k;
 }
-template <bool MIX>
-struct NetKeyPol : KeyLoad {
-  using InT = ulonglong2;
+template <bool MIX, typename In = ulonglong2>
+struct NetKeyPol : KeyLoad<In> {
+  using InT = In;
+  using LoadT = uint64_t;
   using StageT = uint64_t;
   using OutT = uint64_t;
   static constexpr bool kDigArray = false;
@@ -148,9 +153,10 @@ __device__ __forceinline__ uint32_t rangeDigit(uint32_t d, uint32_t dLo, uint32_
     return d;
   }
 }
-template <bool MIX, bool FILT = false>
-struct NetFragPolT : KeyLoad {
-  using InT = ulonglong2;
+template <bool MIX, bool FILT = false, typename In = ulonglong2>
+struct NetFragPolT : KeyLoad<In> {
+  using InT = In;
+  using LoadT = uint64_t;
   using StageT = uint32_t;
   using OutT = uint32_t;
   static constexpr bool kDigArray = false;
@@ -174,9 +180,10 @@ using NetFragPol = NetFragPolT<false>;  // ablation entry (no key mixing)
 // Fragments of keys wider than 32 bits (fragWordFits: keyBits <= 32 + bits,
 // e.g. 6B dense keys = 33 bits): the staged u32 word is the whole fragment
 // and the digit goes to the tile's u16 digit array (no early prefetch).
-template <bool MIX, bool FILT = false>
-struct NetFragDigPolT : KeyLoad {
-  using InT = ulonglong2;
+template <bool MIX, bool FILT = false, typename In = ulonglong2>
+struct NetFragDigPolT : KeyLoad<In> {
+  using InT = In;
+  using LoadT = uint64_t;
   using StageT = uint32_t;
   using OutT = uint32_t;
   static constexpr bool kDigArray = true;
@@ -707,13 +714,13 @@ constexpr size_t packedScatterLds() {
          (size_t)PK_CHUNK_FRAGS * PK_DIGITS * 4;
 }
 
-template <bool MIX, typename CurT>
+template <bool MIX, typename CurT, typename InT = ulonglong2>
 __global__ __launch_bounds__(CL_NTH, ScatterOcc<CL_NTH>::value) void netScatterFragPackedKernel(
-    const ulonglong2 *__restrict__ in, uint64_t n, uint32_t tpb, uint32_t F, uint32_t bits, KeyMix mix,
+    const InT *__restrict__ in, uint64_t n, uint32_t tpb, uint32_t F, uint32_t bits, KeyMix mix,
     CurT *__restrict__ gcur, unsigned long long *out, const CurT *__restrict__ gend,
     const uint32_t *__restrict__ roundMeta, unsigned long long *__restrict__ wideFlag) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  using Pol = NetFragPolT<MIX>;  // the loads of the u32 fragment scatter (keys only, non-temporal)
+  using Pol = NetFragPolT<MIX, false, InT>;  // the loads of the u32 fragment scatter (keys only, non-temporal)
   constexpr uint32_t D = PK_DIGITS, NTH = CL_NTH, IPT = CL_IPT, TILE = NTH * IPT;
   constexpr uint32_t FB = PK_FRAG_BITS, FMASK = (1u << FB) - 1, CF = PK_CHUNK_FRAGS, CW = PK_CHUNK_WORDS;
   static_assert(D == NTH, "packed scatter: one thread per digit");

@@ -94,6 +94,7 @@ void HashJoin::planPasses() {
       size_t freeB = 0, totalB = 0;
       HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
       uint64_t avail = (uint64_t)(freeB * 0.85);
+      avail -= std::min(avail, pendingExpansionBytes());
       if (config.workspaceBudget) avail = std::min<uint64_t>(avail, config.workspaceBudget);
       const uint64_t est = workspaceEstimate(), tuplesB = (n[0] + n[1]) * sizeof(data::Tuple);
       spill.estimate = est;
@@ -344,9 +345,15 @@ void HashJoin::makeJoinPlan() {
       } else if (ctx->onDevice() && e > b) {
         unsigned long long *d = ctx->workspace().getArray<unsigned long long>(3);
         HIP_CHECK(hipMemcpyAsync(d, h, 24, hipMemcpyHostToDevice, ctx->stream()));
-        kernels::keyRidMax(r->getData() + b, e - b, d, ctx->stream());
+        // (A key column is scanned in place, for its key bound only: the plan
+        // that decides whether anything needs its tuples does not exist yet.)
+        kernels::keyRidMax(r->keySource() + b, e - b, d, ctx->stream());
         HIP_CHECK(hipMemcpyAsync(h, d, 24, hipMemcpyDeviceToHost, ctx->stream()));
         HIP_CHECK(hipStreamSynchronize(ctx->stream()));
+        if (r->isKeyColumn()) {  // positional rids
+          h[1] = r->ridBase() + e - 1;
+          h[2] = r->ridBase() + b;
+        }
       } else if (!ctx->onDevice()) {
         const data::Tuple *t = r->getData();
         for (uint64_t i = b; i < e; ++i) {
@@ -383,6 +390,9 @@ void HashJoin::makeJoinPlan() {
                         mx[1]);
   planMaxKey = mx[0];
   planMaxRid = mx[1];
+  plan.keyColumn[0] = innerRelation->isKeyColumn();
+  plan.keyColumn[1] = outerRelation->isKeyColumn();
+  plan.singleDeviceRank = ctx->onDevice() && numberOfNodes == 1;
   // Group joins count in u32 accumulators per inner tuple: a key cannot have 2^32 outer partners.
   JOIN_ASSERT(config.kind != core::JoinKind::Group || outerRelation->getGlobalSize() < (1ull << 32), "HashJoin",
               "JoinConfig.kind = group: %lu outer tuples; the per-group counters are 32 bits wide (fewer than 2^32 "
@@ -458,7 +468,8 @@ void HashJoin::makeJoinPlan() {
     HIP_CHECK(hipMemGetInfo(&freeB, &totalB));
     const std::vector<uint64_t> parts = workspaceParts();
     const uint64_t est = workspaceEstimate();
-    uint64_t want = std::min<uint64_t>(est, (uint64_t)(freeB * 0.85));
+    const uint64_t freeForWorkspace = (uint64_t)(freeB * 0.85);
+    uint64_t want = std::min<uint64_t>(est, freeForWorkspace - std::min(freeForWorkspace, pendingExpansionBytes()));
     if (config.workspaceBudget) want = std::min<uint64_t>(want, config.workspaceBudget);
     // Rewound first: a previous join's buffers are dead once a new join is
     // planned on this context, so the chunks are re-laid out instead of
@@ -493,21 +504,34 @@ int HashJoin::innerKeyRepeats() {
   const uint64_t n = innerRelation->getLocalSize();
   const uint32_t S = (uint32_t)std::min<uint64_t>(n, 65536);
   if (S < 2) return 1;
-  const data::Tuple *t = innerRelation->getData();
   if (ctx->onDevice()) {
     void *ws = ctx->workspace().get(kernels::sampleRepeatsBytes(S));
     auto *cnt = ctx->workspace().getArray<unsigned int>(1);
-    kernels::sampleRepeats(t, n, S, ws, cnt, ctx->stream());
+    kernels::sampleRepeats(innerRelation->keySource(), n, S, ws, cnt, ctx->stream());
     unsigned int h = 0;
     HIP_CHECK(hipMemcpyAsync(&h, cnt, sizeof(h), hipMemcpyDeviceToHost, ctx->stream()));
     HIP_CHECK(hipStreamSynchronize(ctx->stream()));
     return h ? 2 : 1;
   }
+  const data::Tuple *t = innerRelation->getData();
   std::unordered_set<uint64_t> seen;
   seen.reserve(2 * S);
   for (uint32_t i = 0; i < S; ++i)
     if (!seen.insert(t[(uint64_t)((unsigned __int128)i * n / S)].key).second) return 2;
   return 1;
+}
+
+// HBM that key-column sides will still take outside the workspace: a plan
+// that cannot read them in place has each expanded to 16-byte tuples by
+// data::Relation::getData (once; nothing is pending for an expanded side).
+// (A bitmap plan that later falls back to a rid-carrying plan is not foreseen.)
+uint64_t HashJoin::pendingExpansionBytes() const {
+  if (!ctx->onDevice() || plan.readsKeyColumns()) return 0;
+  uint64_t b = 0;
+  for (data::Relation *r : {innerRelation, outerRelation})
+    if (r->isKeyColumn() && !r->expanded() && r->location() == Location::Device)
+      b += r->getLocalSize() * sizeof(data::Tuple);
+  return b;
 }
 
 uint64_t HashJoin::workspaceEstimate() const {
@@ -818,7 +842,7 @@ bool HashJoin::lowKeyBitsSkewed() {
   uint32_t *blockHist = ctx->workspace().getArray<uint32_t>((uint64_t)F * g.blocks);
   if (ctx->onDevice()) {
     uint64_t *d = ctx->workspace().getArray<uint64_t>(F);
-    kernels::netHistogram(innerRelation->getData(), n, bits, g, blockHist, ctx->stream());
+    kernels::netHistogram(innerRelation->keySource(), n, bits, g, blockHist, ctx->stream());
     kernels::digitTotals(blockHist, F, g.blocks, g.blocks, 1, d, ctx->stream());
     HIP_CHECK(hipMemcpyAsync(totals.data(), d, F * 8, hipMemcpyDeviceToHost, ctx->stream()));
     HIP_CHECK(hipStreamSynchronize(ctx->stream()));
@@ -951,8 +975,14 @@ JoinResult HashJoin::run() {
   } watch(ctx->comm());
   utils::setPhase("plan");
   try {
-    if (passes > 1) return runPasses();
-    return runImpl();
+    passes > 1 ? runPasses() : runImpl();
+    // Read off the relations: a key column nobody asked for tuples is still unexpanded.
+    data::Relation *rel[2] = {innerRelation, outerRelation};
+    for (int r = 0; r < 2; ++r)
+      result.keyColumns[r] = !rel[r]->isKeyColumn() ? JoinResult::Tuples
+                             : rel[r]->expanded()   ? JoinResult::Expanded
+                                                    : JoinResult::Native;
+    return result;
   } catch (const std::exception &e) {
     while (!TASK_QUEUE.empty()) TASK_QUEUE.pop();  // tasks are owned (and freed) by runImpl
     ctx->comm()->abort(e.what());
@@ -1007,6 +1037,7 @@ JoinResult HashJoin::runImpl() {
       done = SampledShuffleExchange(env).exchange(run);
     if (!done) {  // a slice overflowed (skew the sample missed): exact from now on
       sampledOverflowed = true;
+      plan.networkExact = true;  // (u32 fragments are written by the sampled pass only: JoinPlan::readsKeyColumns)
       ++result.networkFallbacks;
     }
   }

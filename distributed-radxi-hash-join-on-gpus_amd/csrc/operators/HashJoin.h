@@ -75,6 +75,14 @@ struct JoinResult {
   bool directScatter = false;      // one-sided windows: the scatter kernel wrote into the owners' windows
                                    // (false with ExchangeMode::OneSided = staged send buffer + peer copies,
                                    // e.g. when a split hot partition adds replicas)
+  // How the join read a key-column side (data::Relation::isKeyColumn), inner
+  // then outer: Native = in place and no expansion exists, Expanded = through
+  // the relation's tuple expansion, Tuples = the side is a tuple relation.
+  enum KeyColumnUse : uint8_t { Tuples = 0, Native = 1, Expanded = 2 };
+  KeyColumnUse keyColumns[2] = {Tuples, Tuples};
+  static const char *keyColumnUseName(KeyColumnUse u) {
+    return u == Native ? "native" : u == Expanded ? "expanded" : "tuples";
+  }
 };
 
 // Achievable one-way bandwidth of one xGMI peer link (MI355X: 7 links of
@@ -179,6 +187,8 @@ class HashJoin {
   // Upper estimate of the workspace bytes one run() of this plan carves from
   // the arena (windows, send/wire buffers, local pass output, work lists).
   uint64_t workspaceEstimate() const;
+  // Bytes the key-column sides' tuple expansions will take beside the workspace under this plan.
+  uint64_t pendingExpansionBytes() const;
   std::vector<uint64_t> workspaceParts() const;  // the estimate as one chunk per big buffer
   // Bytes the constructor added to the arena (0 if it already held the estimate).
   uint64_t reservedBytes() const { return reserved; }

@@ -75,6 +75,13 @@ const BitmapJoin::SidePlan &BitmapJoin::sidePlan(uint64_t n, bool exact, uint32_
   return cache.emplace(k, sp).first->second;
 }
 
+// What the histograms and scatters read: a key column in place when no
+// scatter of this plan writes a rid (JoinPlan::readsKeyColumns: one device
+// rank), else the relation's tuples (a key column's expansion).
+kernels::KeySource BitmapJoin::keys(data::Relation *r) const {
+  return plan.readsKeyColumns() ? r->keySource() : kernels::KeySource(r->getData());
+}
+
 // Sampled (or exact) histogram -> device layout of bounded claim slices ->
 // bounded claim scatter of u32 fragments.  Nothing here waits for the device.
 bool BitmapJoin::sideNarrow(data::Relation *r, bool exact, uint32_t elemBytes) const {
@@ -105,7 +112,7 @@ void BitmapJoin::layoutSides(Side *sides, uint32_t count, bool exact, bool narro
     s.geom = sp.geom;
     const uint32_t stride = sp.stride;
     sampled = sampled && stride > 1;
-    in[i] = kernels::SampledInput{s.relation->getData(), n, s.geom, stride, totals + (size_t)i * G * F};
+    in[i] = kernels::SampledInput{keys(s.relation), n, s.geom, stride, totals + (size_t)i * G * F};
     const kernels::SampleScale &sc = sp.sc;
     s.cap = sp.cap;
     // Claims may run past a slice end by up to n before the overflow is seen.
@@ -172,20 +179,20 @@ void BitmapJoin::layoutSides(Side *sides, uint32_t count, bool exact, bool narro
 void BitmapJoin::scatterSide(Side &s) {
   const kernels::KeyMix mix{plan.keyMix ? 1u : 0u, plan.keyBits};
   if (s.packed) {  // packed fragment words in whole chunks; a fragment above 20 bits raises the dup flag
-    kernels::netScatterFragPacked(s.relation->getData(), s.relation->getLocalSize(), plan.networkBits, s.geom,
+    kernels::netScatterFragPacked(keys(s.relation), s.relation->getLocalSize(), plan.networkBits, s.geom,
                                   const_cast<void *>(s.slices.cur), reinterpret_cast<uint64_t *>(s.frags),
                                   ctx->stream(), mix, s.slices.end, s.slices.narrow, s.slices.roundMeta,
                                   &counters->dup);
     return;
   }
   if (s.elemBytes == 8) {  // CompressedTuples (fragment << keyShift | rid) into the same bounded claim slices
-    kernels::netScatter(s.relation->getData(), s.relation->getLocalSize(), plan.networkBits, plan.keyShift, s.geom, 0,
+    kernels::netScatter(keys(s.relation), s.relation->getLocalSize(), plan.networkBits, plan.keyShift, s.geom, 0,
                         s.geom.blocks, const_cast<void *>(s.slices.cur), reinterpret_cast<uint64_t *>(s.frags),
                         ctx->stream(), plan.keyBits, mix, s.slices.end, s.slices.narrow ? 1 : 0, true,
                         s.slices.roundMeta);
     return;
   }
-  kernels::netScatterFrag(s.relation->getData(), s.relation->getLocalSize(), plan.networkBits, s.geom, 0,
+  kernels::netScatterFrag(keys(s.relation), s.relation->getLocalSize(), plan.networkBits, s.geom, 0,
                           s.geom.blocks, const_cast<void *>(s.slices.cur), s.frags, ctx->stream(), plan.keyBits, mix,
                           s.slices.end, s.slices.narrow ? 1 : 0, s.slices.roundMeta);
 }
@@ -222,7 +229,7 @@ BitmapJoin::Outcome BitmapJoin::runDeviceGroups(bool exact) {
       both[i].geom = sp.geom;
       sc[i] = sp.sc;
       sampled = sampled && sp.stride > 1;
-      in[i] = kernels::SampledInput{both[i].relation->getData(), n, sp.geom, sp.stride, totals + (size_t)i * G * F};
+      in[i] = kernels::SampledInput{keys(both[i].relation), n, sp.geom, sp.stride, totals + (size_t)i * G * F};
     }
     utils::faultPoint("network");
     tl.beginSplitAt("HLOCAL", "HILOCAL", (double)inner->getLocalSize(), "HOLOCAL", (double)outer->getLocalSize(),
@@ -320,7 +327,7 @@ BitmapJoin::Outcome BitmapJoin::runDeviceGroups(bool exact) {
     for (int i = 0; i < 2; ++i) {
       Side &sd = both[i];
       sd.slices.count = g.cap[i];  // the bitmap kernels' flat-walk choice: tuples per partition
-      kernels::netScatterFragRange(sd.relation->getData(), sd.relation->getLocalSize(), nb, sd.geom,
+      kernels::netScatterFragRange(keys(sd.relation), sd.relation->getLocalSize(), nb, sd.geom,
                                    const_cast<void *>(sd.slices.cur), sd.frags, st, plan.keyBits, mix, sd.slices.end,
                                    narrow, g.lo, g.n);
     }

@@ -112,6 +112,7 @@ class BitmapJoin {
   void layoutSides(Side *sides, uint32_t count, bool exact, bool narrowOk);
   void scatterSide(Side &s);
   bool sideNarrow(data::Relation *r, bool exact, uint32_t elemBytes = 4) const;
+  kernels::KeySource keys(data::Relation *r) const;
   // Set mode: the kind's count from hits / misses (checked against |S|).
   void finishSet(Outcome &o, uint64_t hits, uint64_t misses) const;
   Outcome runDevice(bool exact);

@@ -87,6 +87,11 @@ void NetworkPartitioning::partition(data::Relation *relation, data::Window *wind
       ctx->copy(base, xp.digitBase.data(), xp.digitBase.size() * 8, true, false);
     }
     kernels::netGroupCursors(local->blockHistogram(), F, g.blocks, bpc, base, gcur, narrow, ctx->stream());
+    // Key-only words carry no rid: a key column is read in place (JoinPlan::readsKeyColumns);
+    // CompressedTuples and wide tuples need the relation's tuples.
+    const kernels::KeySource keys = plan.keyOnly && !plan.wide && plan.readsKeyColumns()
+                                        ? relation->keySource()
+                                        : kernels::KeySource(relation->getData());
     for (uint32_t c = 0; c < chunks; ++c) {
       const uint32_t b0 = c * bpc, b1 = std::min(g.blocks, b0 + bpc);
       const int narrowMode = narrow ? 1 : 0;
@@ -94,7 +99,7 @@ void NetworkPartitioning::partition(data::Relation *relation, data::Window *wind
         kernels::netScatterWide(relation->getData(), n, bits, g, b0, b1, gcur + c * perChunk,
                                 static_cast<data::Tuple *>(send), ctx->stream(), mix, nullptr, narrowMode);
       else
-        kernels::netScatter(relation->getData(), n, bits, plan.keyShift, g, b0, b1, gcur + c * perChunk,
+        kernels::netScatter(keys, n, bits, plan.keyShift, g, b0, b1, gcur + c * perChunk,
                             static_cast<uint64_t *>(send), ctx->stream(), plan.keyBits, mix, nullptr, narrowMode,
                             !plan.keyOnly);
       replicate(c);

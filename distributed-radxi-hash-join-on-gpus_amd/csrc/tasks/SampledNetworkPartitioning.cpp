@@ -71,7 +71,7 @@ void SampledNetworkPartitioning::sample() {
     s.sc = sp.sc;
     s.capacityTotal = sp.bound;
     s.groupTotalsDev = totals + (size_t)k * G * F;
-    in[k] = kernels::SampledInput{s.relation->getData(), n, s.geom, s.stride, s.groupTotalsDev};
+    in[k] = kernels::SampledInput{keys(s), n, s.geom, s.stride, s.groupTotalsDev};
     bothSampled = bothSampled && s.stride > 1;
   }
   // One span for both histograms, charged to HILOCAL / HOLOCAL by tuples.
@@ -90,6 +90,13 @@ void SampledNetworkPartitioning::sample() {
     }
   }
   ctx->timeline().end("HLOCAL", st);
+}
+
+// What the histogram and the scatter of a side read: a key column in place
+// when this plan's scatter writes no rid, else the relation's tuples (a key
+// column's expansion).
+kernels::KeySource SampledNetworkPartitioning::keys(const Side &s) const {
+  return plan.readsKeyColumns() ? s.relation->keySource() : kernels::KeySource(s.relation->getData());
 }
 
 // Round-interleaved slices (kernels::RoundMap) for windows the local pass
@@ -174,14 +181,14 @@ void SampledNetworkPartitioning::scatterSide(int k) {
   const char *key = k == 0 ? "MIMAINPART" : "MOMAINPART";
   ctx->timeline().begin(key, ctx->stream());
   if (plan.fragments)  // count-only: u32 key fragments (key >> networkBits), no rid
-    kernels::netScatterFrag(s.relation->getData(), n, plan.networkBits, s.geom, 0, s.geom.blocks, s.gcur,
+    kernels::netScatterFrag(keys(s), n, plan.networkBits, s.geom, 0, s.geom.blocks, s.gcur,
                             static_cast<uint32_t *>(s.window->getData()), ctx->stream(), plan.keyBits, mix, s.gend, nm,
                             s.roundMeta);
   else if (plan.wide)
     kernels::netScatterWide(s.relation->getData(), n, plan.networkBits, s.geom, 0, s.geom.blocks, s.gcur,
                             static_cast<data::Tuple *>(s.window->getData()), ctx->stream(), mix, s.gend, nm);
   else
-    kernels::netScatter(s.relation->getData(), n, plan.networkBits, plan.keyShift, s.geom, 0, s.geom.blocks, s.gcur,
+    kernels::netScatter(keys(s), n, plan.networkBits, plan.keyShift, s.geom, 0, s.geom.blocks, s.gcur,
                         static_cast<uint64_t *>(s.window->getData()), ctx->stream(), plan.keyBits, mix, s.gend, nm,
                         !plan.keyOnly, s.roundMeta);
   ctx->timeline().end(key, ctx->stream());

@@ -83,6 +83,7 @@ class SampledNetworkPartitioning {
     uint64_t capacityTotal = 0;  // window slots: the layout's capacity bound
   };
   void finishPlan(Side &s);
+  kernels::KeySource keys(const Side &s) const;
 
   core::ExecContext *ctx;
   const core::JoinPlan &plan;

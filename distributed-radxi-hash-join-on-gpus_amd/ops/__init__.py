@@ -1,6 +1,9 @@
 """Tensor-level entry points of the gfx950 kernels (device tensors) and their
 host twins (CPU tensors).  Tuples are int64 tensors of shape [n, 2] holding
-(key, rid) — the 16-byte ``hpcjoin::data::Tuple`` layout.
+(key, rid) — the 16-byte ``hpcjoin::data::Tuple`` layout.  The whole-engine
+ops (``join_count``, ``join``, the semi / anti / outer / group joins) also take
+a 1-D int64 key column for either side: its rids are the positions, and the
+plans that carry no rid read it in place (``Relation.from_keys``).
 
     values, begin = radix_partition(tuples, bits=10)      # network pass
     v2, begin2 = local_partition(values, begin, 32, 9)   # local pass
@@ -36,7 +39,7 @@ def generate(n: int, distribution: str = "UNIQUE", seed: int = 1234, domain: int
 
 
 def radix_histogram(tuples: torch.Tensor, bits: int) -> torch.Tensor:
-    """Counts of ``key & (2^bits - 1)`` (LocalHistogram)."""
+    """Counts of ``key & (2^bits - 1)`` (LocalHistogram); ``tuples`` may be a 1-D key column."""
     return _C().ops.net_histogram(tuples.contiguous(), bits)
 
 
@@ -155,13 +158,21 @@ def npj_join(R: torch.Tensor, S: torch.Tensor) -> torch.Tensor:
     return _C().ops.npj_join(R.contiguous(), S.contiguous())
 
 
+def _relation(C, t: torch.Tensor):
+    """``[n, 2]`` (key, rid) tuples, or a 1-D int64 key column whose rids are the positions (read in place by the
+    plans that carry no rid, ``Relation.from_keys``)."""
+    if t.dim() == 1:
+        return C.Relation.from_keys(t.contiguous(), t.shape[0], 0)
+    return C.Relation.from_tensor(t.contiguous(), t.shape[0])
+
+
 def _engine(inner: torch.Tensor, outer: torch.Tensor, config=None):
     C = _C()
     on_dev = inner.is_cuda
     dev = (inner.device.index or 0) if on_dev else -1
     ctx = C.ExecContext("device" if on_dev else "host", dev, C.LocalCommunicator())
-    R = C.Relation.from_tensor(inner.contiguous(), inner.shape[0])
-    S = C.Relation.from_tensor(outer.contiguous(), outer.shape[0])
+    R = _relation(C, inner)
+    S = _relation(C, outer)
     return C.HashJoin(R, S, ctx, config or C.JoinConfig())
 
 
@@ -263,8 +274,8 @@ def _group_join(inner, outer, values, rid_offset: int, config=None) -> torch.Ten
     on_dev = inner.is_cuda
     ctx = C.ExecContext("device" if on_dev else "host", (inner.device.index or 0) if on_dev else -1,
                         C.LocalCommunicator())
-    R = C.Relation.from_tensor(inner.contiguous(), inner.shape[0])
-    S = C.Relation.from_tensor(outer.contiguous(), outer.shape[0])
+    R = _relation(C, inner)
+    S = _relation(C, outer)
     j = C.HashJoin(R, S, ctx, cfg)
     if values is None:
         j.run()
@@ -318,8 +329,8 @@ def group_join_agg(inner: torch.Tensor, outer: torch.Tensor, columns, aggs, rid_
     on_dev = inner.is_cuda
     ctx = C.ExecContext("device" if on_dev else "host", (inner.device.index or 0) if on_dev else -1,
                         C.LocalCommunicator())
-    R = C.Relation.from_tensor(inner.contiguous(), inner.shape[0])
-    S = C.Relation.from_tensor(outer.contiguous(), outer.shape[0])
+    R = _relation(C, inner)
+    S = _relation(C, outer)
     j = C.HashJoin(R, S, ctx, cfg)
     _, rows = j.join_group_agg(ctx, list(columns), [str(a) for a in aggs], rid_offset, outer.shape[0])
     return rows
@@ -345,8 +356,8 @@ def _kind_join_rows(inner, outer, kind: str, inner_rows, outer_rows, rid_offset:
     on_dev = inner.is_cuda
     ctx = C.ExecContext("device" if on_dev else "host", (inner.device.index or 0) if on_dev else -1,
                         C.LocalCommunicator())
-    R = C.Relation.from_tensor(inner.contiguous(), inner.shape[0])
-    S = C.Relation.from_tensor(outer.contiguous(), outer.shape[0])
+    R = _relation(C, inner)
+    S = _relation(C, outer)
     j = C.HashJoin(R, S, ctx, cfg)
     if inner_rows is None:  # semi / anti: the inner payload is never read
         inner_rows = torch.empty((0, 4), dtype=torch.int64, device=outer_rows.device)
