@@ -104,8 +104,11 @@ JoinPlan makePlan(const JoinConfig &cfg, uint32_t numberOfNodes, uint64_t global
               "networkBits=%u out of range", p.networkBits);
   JOIN_ASSERT(p.localBits <= Configuration::GPU_MAX_FANOUT_BITS, "Plan", "localBits=%u out of range", p.localBits);
 
-  const uint32_t ridBits = maxRid == ~0ull ? 64 : ceilLog2(maxRid + 1);
-  const uint32_t keyBits = maxKey == ~0ull ? 64 : ceilLog2(maxKey + 1);
+  // Bits of the largest value.  From 2^63 up the answer is 64, and ceilLog2 must not be asked: it would compare
+  // against 1 << 64 (a key such as 0xFFFFFFFFFFFFFFFE made it spin for ever).
+  auto bitsOf = [](uint64_t v) { return v >= (1ull << 63) ? 64u : ceilLog2(v + 1); };
+  const uint32_t ridBits = bitsOf(maxRid);
+  const uint32_t keyBits = bitsOf(maxKey);
   p.keyBits = keyBits;
   // Mixed keys stay below 2^keyBits; a full 64-bit domain could map a key onto
   // the wide format's reserved empty marker, so mixing needs keyBits < 64.

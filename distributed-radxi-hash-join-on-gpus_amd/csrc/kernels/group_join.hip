@@ -653,7 +653,9 @@ static BPArgs groupArgs(const BPArgs &args, const char *who) {
 static void groupColumnsCheck(const GroupColumns &cols, const char *who) {
   HJ_CHECK(cols.n <= GROUP_MAX_COLUMNS, "%s: %u value columns (0 to %u)", who, cols.n, GROUP_MAX_COLUMNS);
   for (uint32_t c = 0; c < cols.n; ++c)
-    HJ_CHECK(cols.col[c] && cols.stride[c] >= 1 && cols.agg[c] <= GROUP_MAX && cols.dtype[c] <= GROUP_DTYPE_MAX &&
+    // (cols.rows == 0: a column without storage; the callers' cover checks then admit no outer tuple to read it for.)
+    HJ_CHECK((cols.col[c] || cols.rows == 0) && cols.stride[c] >= 1 && cols.agg[c] <= GROUP_MAX &&
+                 cols.dtype[c] <= GROUP_DTYPE_MAX &&
                  reinterpret_cast<uintptr_t>(cols.col[c]) % groupDtypeBytes(cols.dtype[c]) == 0,
              "%s: column %u needs aligned values, a stride >= 1, an aggregate (sum, min, max) and an element type "
              "(int64, int32, float64, float32)",

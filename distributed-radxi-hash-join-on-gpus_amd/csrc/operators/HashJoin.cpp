@@ -881,7 +881,9 @@ void HashJoin::setGroupColumns(const kernels::GroupColumns &c, const char *who) 
               "(group_columns) = %u; set group_columns to the number of columns before constructing the join",
               who, c.n, plan.groupColumns);
   for (uint32_t i = 0; i < c.n; ++i) {
-    JOIN_ASSERT(c.col[i] && c.stride[i] >= 1, "HashJoin", "%s: column %u needs values and a positive stride", who, i);
+    // (A column of no rows has no storage: nothing reads it, since the cover check below then admits no outer rid.)
+    JOIN_ASSERT((c.col[i] || c.rows == 0) && c.stride[i] >= 1, "HashJoin",
+                "%s: column %u needs values and a positive stride", who, i);
     JOIN_ASSERT(c.agg[i] <= kernels::GROUP_MAX, "HashJoin", "%s: column %u has no aggregate %u", who, i, c.agg[i]);
     JOIN_ASSERT(c.dtype[i] <= kernels::GROUP_DTYPE_MAX, "HashJoin",
                 "%s: column %u has no element type %u (int64, int32, float64, float32)", who, i, c.dtype[i]);

@@ -507,11 +507,23 @@ void BuildProbe::execute() {
   performance::Measurements::add("BPBUILDELEM", wb, "tuples");
   performance::Measurements::add("BPPROBEELEM", wp, "tuples");
   if (!dev) {
-    hostCursor = 0;
     args.outCursor = reinterpret_cast<unsigned long long *>(&hostCursor);
     tl.begin("BPTASKTIME");
     tl.beginSplit("BPKERNEL", "BPBUILD", wb, "BPPROBE", wp);
-    matches = host::buildProbe(args);
+    for (;;) {
+      hostCursor = 0;
+      matches = host::buildProbe(args);
+      if (!plan.materialize || hostOut || hostCursor <= outputCapacity) break;
+      // more pairs than the default capacity (repeated keys): once more, exactly sized, as the device path's
+      // collect() does -- the stores past the capacity were dropped, and getOutput() would be read beyond it.
+      // (The undersized buffer stays in the arena until the next reset: host twin, one extra build/probe.)
+      // hostOut is the caller's buffer and cannot grow: pairs past its capacity stay dropped, outputCount
+      // keeps the true total and collect() reports it as outputOverflow, as on the device.
+      outputCapacity = hostCursor;
+      outPairs = static_cast<ulonglong2 *>(ws.get(outputCapacity * sizeof(ulonglong2)));
+      args.outPairs = outPairs;
+      args.outCapacity = outputCapacity;
+    }
     tl.end("BPKERNEL");
     tl.end("BPTASKTIME");
     outputCount = hostCursor;
